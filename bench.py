@@ -17,6 +17,10 @@ HBM before the timed region starts, output left in HBM.  K steps are timed per c
 maximum over ranks counts.  `value` = corpus bytes * K / that time.  One JSON line is printed by rank 0 (DESIGN.md section 6
 defines every field).  `--codec brotli|zstd|flzma2` with `--bytes/--level/--corpus` runs ONE codec on a chosen workload
 (configs C4 / C5 and experiments); the default run is the metric.
+
+A plain run times the headline leg only (zstd-L3, or the `--codec` leg) and reports its rate, size and ratio.  `--full` adds what
+the headline figure does not need: the Fast-LZMA2 leg, the decode checks, `gpu_decode`, `ratio_vs_ref`, `roofline`, the CPU
+baselines and `real_data`.  `--dump-outputs DIR` writes the compressed stream of each leg's last timed step (dump_outputs).
 """
 import argparse
 import json
@@ -32,6 +36,30 @@ HBM_PEAK_GBS = 8000.0          # MI355X HBM3E peak, /opt/skills/guides/MI355X_MI
 ENWIK9_BYTES = 1_000_000_000
 SILESIA_BYTES = 211_900_000
 DEFAULTS = {"zstd": (3, "text-zipf", ENWIK9_BYTES), "flzma2": (5, "silesia-like", SILESIA_BYTES), "brotli": (6, "web-text", ENWIK9_BYTES)}
+
+DUMP_WINDOW = 32 * 1024        # --dump-outputs: bytes per sampled window of a compressed stream
+DUMP_WINDOWS = 128             # windows per stream: 4 MiB = 16 MB as float32, so the two legs of --full stay under 64 MB
+DUMP_SEED = 20260921
+
+
+def load_corpus_module(root):
+    """<root>/7-zip-zstd_amd/corpus (the stand-in corpora).  That module builds its generator library next to corpus_gen.c on first use; the
+    benchmark never writes into the tree (it may be read-only), so where the library there is missing or older than its source, the module
+    is pointed at a private copy of the source in a temporary directory (removed at exit) and builds the library there."""
+    import atexit
+    import importlib.util
+    import shutil
+    import tempfile
+    here = os.path.join(root, "7-zip-zstd_amd", "corpus")
+    spec = importlib.util.spec_from_file_location("sevenzip_zstd_amd_corpus", os.path.join(here, "__init__.py"))
+    mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
+    so, src = os.path.join(here, "libgc_corpus.so"), os.path.join(here, "corpus_gen.c")
+    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
+        tmp = tempfile.mkdtemp(prefix="gc_corpus_")
+        atexit.register(shutil.rmtree, tmp, True)
+        shutil.copy(src, tmp)
+        mod.HERE = tmp
+    return mod
 
 
 def _oracle():
@@ -72,6 +100,26 @@ def cpu_baseline(codec, x, level):
     return ({"value": round(sample.size / tm / 1e6, 1), "unit": "MB/s", "cores": thr, "kind": "reference",
              "sample": "BROTLIMT_compressCCtx quality %d on the first %d bytes of the corpus, one run, %d threads; single thread (8 MiB): %.1f MB/s"
                        % (level, sample.size, thr, one.size / t1 / 1e6)}, (len(cm), sample.size))
+
+
+def dump_outputs(out_dir, tag, stream):
+    """The last timed step's output as a caller receives it, a compressed stream, written as float arrays under out_dir:
+    <tag>_stream_size.npy (float64 [bytes]), <tag>_stream_sample.npy (float32 [windows, width]: the whole stream if it is at most
+    DUMP_WINDOWS x DUMP_WINDOW bytes, else DUMP_WINDOWS windows of DUMP_WINDOW bytes, the first one and the rest at seeded offsets)
+    and <tag>_stream_sample_offsets.npy (float64: where each window starts)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(stream.size)
+    if n <= DUMP_WINDOW * DUMP_WINDOWS:
+        offsets, width = np.zeros(1, dtype=np.int64), n
+    else:
+        slots = n // DUMP_WINDOW
+        rest = 1 + np.random.default_rng(DUMP_SEED).choice(slots - 1, DUMP_WINDOWS - 1, replace=False)
+        offsets, width = np.sort(np.concatenate([[0], rest])).astype(np.int64) * DUMP_WINDOW, DUMP_WINDOW
+    sample = stream[offsets[:, None] + np.arange(width)]
+    np.save(os.path.join(out_dir, tag + "_stream_size.npy"), np.array([n], dtype=np.float64))
+    np.save(os.path.join(out_dir, tag + "_stream_sample.npy"), sample.astype(np.float32))
+    np.save(os.path.join(out_dir, tag + "_stream_sample_offsets.npy"), offsets.astype(np.float64))
 
 
 def _pmc_lookup(section, n, kname):
@@ -187,8 +235,10 @@ def run_codec(codec, level, corpus_name, total, args, env):
                 mf_ms[k] = mf_ms.get(k, 0.0) + v
     barrier()
     elapsed = time.perf_counter() - t0
-    # ---- outside the timed region: max over ranks, gather of the compressed ranges, decode of the concatenation
+    # ---- outside the timed region: max over ranks, gather of the compressed ranges (--full, --dump-outputs), decode of the concatenation (--full)
     sizes = [csize]
+    want_stream = args.full or bool(args.dump_outputs)
+    stream = None
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -197,19 +247,38 @@ def run_codec(codec, level, corpus_name, total, args, env):
         all_sz = [torch.zeros_like(sz) for _ in range(world)]
         dist.all_gather(all_sz, sz)
         sizes = [int(v.item()) for v in all_sz]
-        pad = max(sizes) + 1
-        mine = torch.zeros(pad, dtype=torch.uint8, device=dev); mine[:csize] = d_dst[:csize]
-        parts = [torch.empty(pad, dtype=torch.uint8, device=dev) for _ in range(world)]
-        dist.all_gather(parts, mine)
-        stream = np.concatenate([p[:z].cpu().numpy() for p, z in zip(parts, sizes)]) if rank == 0 else None
-    else:
+        if want_stream:
+            pad = max(sizes) + 1
+            mine = torch.zeros(pad, dtype=torch.uint8, device=dev); mine[:csize] = d_dst[:csize]
+            parts = [torch.empty(pad, dtype=torch.uint8, device=dev) for _ in range(world)]
+            dist.all_gather(parts, mine)
+            stream = np.concatenate([p[:z].cpu().numpy() for p, z in zip(parts, sizes)]) if rank == 0 else None
+    elif want_stream:
         stream = d_dst[:csize].cpu().numpy()
     if rank != 0:
         enc.close()
         return None
-    if fl2:
+    if fl2 and stream is not None:
         stream = np.concatenate([stream, np.zeros(1, dtype=np.uint8)])         # the single LZMA2 end marker
-    total_csize = int(stream.size)
+    total_csize = sum(sizes) + (1 if fl2 else 0)
+    value = total * args.steps / elapsed / 1e6
+    ratio = total / total_csize
+    frames = ("8 MiB match-finder frames" + (", overlapping (stride %d MiB) in groups of %d MiB" % ((2 if (codec == "zstd" and level >= 20) or (codec == "flzma2" and level >= 8) else 4), grain >> 20) if grain > (8 << 20) else "")) if mf_ms else "block-local match finder"
+    res = {
+        "metric": ("brotli-q%d (brotli-mt framed)" % level if br else "flzma2-L%d" % level if fl2 else "zstd-L%d" % level) + " compression throughput (input MB/s)",
+        "value": round(value, 1), "unit": "MB/s", "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "workload": ("Brotli quality %d, synthetic web-text (%s, %d B), %d MiB brotli-mt chunks" % (level, corpus_name, total, max(level, 1))) if br else
+                    ("Fast-LZMA2 level %d, Silesia stand-in (%s, %d B), %s, 4 KiB range-coder chunks grouped into LZMA2 chunks, "
+                     "model segments per gc_api.hip flzma2_seg_log" % (level, corpus_name, total, frames)) if fl2 else
+                    ("zstd level %d, %s stand-in (%s, %d B), 128 KiB blocks in independent %s" % (level, "enwik9" if total == ENWIK9_BYTES else "enwik", corpus_name, total, frames)),
+        "bytes_total": total, "bytes_per_gpu": [b - a for a, b in S.shard_ranges(total, world, grain)], "shard_grain": grain,
+        "compressed_bytes": total_csize, "compressed_bytes_per_gpu": sizes, "ratio": round(ratio, 4),
+    }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "%s_l%d" % (codec, level), stream)
+    if not args.full:
+        enc.close()
+        return res
     for k in kern_ms:
         kern_ms[k] /= max(args.steps, 1)
     for k in mf_ms:
@@ -279,8 +348,6 @@ def run_codec(codec, level, corpus_name, total, args, env):
                                            "achieved": round(algo / (best * 1e-3) / 1e9, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(algo / (best * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
                                            "traffic": None, "algorithmic_bytes_per_launch": algo}}
                 dec.close(); del d_c, d_y
-    value = total * args.steps / elapsed / 1e6
-    ratio = total / total_csize
     # dominant kernel of rank 0 = the longest single kernel by live HIP-event timing; algorithmic bytes per launch =
     # (1 + 1/ratio) bytes per input byte x the bytes one launch of it processes (this rank's range)
     per_kernel = {k: v for k, v in kern_ms.items() if k != "total"}
@@ -318,18 +385,7 @@ def run_codec(codec, level, corpus_name, total, args, env):
         ours = enc.finish()
         ratio_vs_ref = {"note": "both encoders on the first sample_bytes of the corpus", "sample_bytes": ref[1], "ref_bytes": ref[0], "ours_bytes": ours,
                         "ours_over_ref": round(ours / ref[0], 4), "pass_le_1.02": bool(ours <= 1.02 * ref[0])}
-    frames = ("8 MiB match-finder frames" + (", overlapping (stride %d MiB) in groups of %d MiB" % ((2 if (codec == "zstd" and level >= 20) or (codec == "flzma2" and level >= 8) else 4), grain >> 20) if grain > (8 << 20) else "")) if mf_ms else "block-local match finder"
-    res = {
-        "metric": ("brotli-q%d (brotli-mt framed)" % level if br else "flzma2-L%d" % level if fl2 else "zstd-L%d" % level) + " compression throughput (input MB/s)",
-        "value": round(value, 1), "unit": "MB/s", "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "workload": ("Brotli quality %d, synthetic web-text (%s, %d B), %d MiB brotli-mt chunks" % (level, corpus_name, total, max(level, 1))) if br else
-                    ("Fast-LZMA2 level %d, Silesia stand-in (%s, %d B), %s, 4 KiB range-coder chunks grouped into LZMA2 chunks, "
-                     "model segments per gc_api.hip flzma2_seg_log" % (level, corpus_name, total, frames)) if fl2 else
-                    ("zstd level %d, %s stand-in (%s, %d B), 128 KiB blocks in independent %s" % (level, "enwik9" if total == ENWIK9_BYTES else "enwik", corpus_name, total, frames)),
-        "bytes_total": total, "bytes_per_gpu": [b - a for a, b in S.shard_ranges(total, world, grain)], "shard_grain": grain,
-        "compressed_bytes": total_csize, "compressed_bytes_per_gpu": sizes, "ratio": round(ratio, 4),
-        "decodes_under_reference": decodes, "gpu_decode": gpu_decode, "ratio_vs_ref": ratio_vs_ref, "roofline": roofline, "cpu_baseline": cpu,
-    }
+    res.update({"decodes_under_reference": decodes, "gpu_decode": gpu_decode, "ratio_vs_ref": ratio_vs_ref, "roofline": roofline, "cpu_baseline": cpu})
     enc.close()
     return res
 
@@ -381,15 +437,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--codec", default="", choices=["", "zstd", "flzma2", "brotli"], help="run ONE codec (default: the metric = zstd-L3 enwik9 + flzma2-L5 Silesia)")
+    ap.add_argument("--codec", default="", choices=["", "zstd", "flzma2", "brotli"], help="run ONE codec (default: the metric, zstd-L3 enwik9; with --full also flzma2-L5 Silesia)")
     ap.add_argument("--bytes", type=int, default=0, help="corpus bytes (whole job; default: the codec's BASELINE workload)")
     ap.add_argument("--corpus", default="")
     ap.add_argument("--level", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-decode-check", action="store_true")
+    ap.add_argument("--full", action="store_true", help="besides the timed headline leg: the Fast-LZMA2 leg of the metric, decode checks, gpu_decode, ratio_vs_ref, "
+                                                        "roofline, CPU baselines, real_data")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines (and no real_data)")
+    ap.add_argument("--no-decode-check", action="store_true", help="with --full: no decode checks (and no gpu_decode)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write each leg's compressed stream of the last timed step to DIR/*.npy (dump_outputs)")
     ap.add_argument("--shard-of", default="", help="N1,N2,...: ONE GPU times every rank's range of an N-way split (both legs of the metric, or --codec) and prints the predicted "
                                                    "aggregate MB/s and efficiency per N instead of the bench line (multi-GPU readiness without an 8-GPU node)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import __graft_entry__ as g
@@ -411,8 +472,8 @@ def main():
         dist.barrier()
     pkg = g.load_package()
     from importlib import util as _u
-    spec = _u.spec_from_file_location("sevenzip_zstd_amd_corpus", os.path.join(ROOT, "7-zip-zstd_amd", "corpus", "__init__.py"))
-    corpus_mod = _u.module_from_spec(spec); spec.loader.exec_module(corpus_mod)
+    corpus_mod = load_corpus_module(ROOT)
+    sys.modules[corpus_mod.__name__] = corpus_mod          # (oracle.corpus, used by --full, takes this one instead of loading its own)
     spec = _u.spec_from_file_location("sevenzip_zstd_amd.sharding", os.path.join(ROOT, "7-zip-zstd_amd", "sharding.py"))
     sharding = _u.module_from_spec(spec); spec.loader.exec_module(sharding)
     env = {"rank": rank, "local_rank": local_rank, "world": world, "dist": dist, "dev": torch.device("cuda", local_rank), "pkg": pkg,
@@ -437,7 +498,7 @@ def main():
         main_res, extra = one(args.codec), None
     else:
         main_res = one("zstd")
-        extra = one("flzma2")
+        extra = one("flzma2") if args.full else None
     if rank == 0:
         line = {
             "metric": main_res["metric"] if args.codec else "compress MB/s + ratio-vs-ref, enwik9 zstd-L3 & Silesia flzma2-L5 (value = the zstd-L3 enwik9 leg; flzma2_l5_silesia = the other leg)",
@@ -447,12 +508,13 @@ def main():
             "config": {"workload": main_res["workload"], "bytes_total": main_res["bytes_total"], "bytes_per_gpu": main_res["bytes_per_gpu"],
                        "shard_grain": main_res["shard_grain"], "parallelism": "range-shard x%d at the codec grain, rank-ordered concatenation, no data-path collective" % world},
             "compressed_bytes": main_res["compressed_bytes"], "compressed_bytes_per_gpu": main_res["compressed_bytes_per_gpu"], "ratio": main_res["ratio"],
-            "decodes_under_reference": main_res["decodes_under_reference"], "gpu_decode": main_res.get("gpu_decode"), "ratio_vs_ref": main_res["ratio_vs_ref"],
-            "roofline": main_res["roofline"], "cpu_baseline": main_res["cpu_baseline"],
         }
+        if args.full:
+            line.update({"decodes_under_reference": main_res["decodes_under_reference"], "gpu_decode": main_res.get("gpu_decode"), "ratio_vs_ref": main_res["ratio_vs_ref"],
+                         "roofline": main_res["roofline"], "cpu_baseline": main_res["cpu_baseline"]})
         if extra is not None:
             line["flzma2_l5_silesia"] = extra
-        if not args.codec and world == 1 and not args.no_cpu_baseline:
+        if args.full and not args.codec and world == 1 and not args.no_cpu_baseline:
             line["real_data"] = real_data_check(pkg, local_rank)
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -1,5 +1,5 @@
 """Config C1 under the REAL host: the reference's own `7z` console program (built by oracle/build_ref_7z.sh from
-/root/reference into oracle/_ref/host7z/, test infrastructure) loads the plugin from its Codecs/ directory the way the product
+the reference tree into oracle/_ref/host7z/, test infrastructure) loads the plugin from its Codecs/ directory the way the product
 does (CPP/7zip/UI/Common/LoadCodecs.cpp:531-650), lists its methods (`7z i`), and runs `7z a -m0=<method> -mx<level>` through
 the plugin's ICompressCoder::Code / SetCoderProperties / WriteCoderProperties (CPP/7zip/Archive/7z/7zEncode.cpp:160-304);
 `7z t` / `7z x` then decode the archive with the host's own built-in decoders (decoder lookup is by method id,
@@ -25,12 +25,17 @@ def _have_host():
     return os.path.exists(os.path.join(HOST, "7z")) and os.path.exists(os.path.join(HOST, "7z.so"))
 
 
+def _build_host():
+    """oracle/build_ref_7z.sh: all four binaries from the reference tree; it exits with 3 and builds nothing where that tree is absent."""
+    r = subprocess.run(["bash", os.path.join(ROOT, "oracle", "build_ref_7z.sh"), HOST], capture_output=True, text=True)
+    assert r.returncode in (0, 3), r.stderr
+
+
 @pytest.fixture(scope="module")
 def host_dir(tmp_path_factory):
     """A private install directory: 7z + 7z.so + Codecs/ (the host looks for Codecs/ next to its own binary)."""
     if not _have_host():
-        if os.path.isdir("/root/reference/CPP"):
-            subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "_ref/host7z/7z"], check=True, capture_output=True)
+        subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True, capture_output=True)      # (builds nothing where the reference tree is absent)
         if not _have_host():
             pytest.skip("reference host not built (oracle/_ref/host7z)")
     d = tmp_path_factory.mktemp("host7z")
@@ -45,8 +50,7 @@ def host_dir_nozstd(tmp_path_factory, host_dir):
     """The same host with a format/codec bundle that has no ZSTD codec of its own (oracle/build_ref_7z.sh links it without ZstdRegister.o),
     like mainline 7-Zip: method id 4F71101 then resolves to the plugin for encoding AND decoding."""
     if not os.path.exists(os.path.join(HOST, "7z_nozstd.so")):
-        if os.path.isdir("/root/reference/CPP"):
-            subprocess.run(["bash", os.path.join(ROOT, "oracle", "build_ref_7z.sh"), HOST], check=True, capture_output=True, env=dict(os.environ, REF_ROOT="/root/reference"))
+        _build_host()
         if not os.path.exists(os.path.join(HOST, "7z_nozstd.so")):
             pytest.skip("reference host without zstd not built (oracle/_ref/host7z/7z_nozstd.so)")
     d = tmp_path_factory.mktemp("host7z_nozstd")
@@ -61,8 +65,7 @@ def host_dir_nobrotli(tmp_path_factory, host_dir):
     """The host with a bundle that has no BROTLI codec of its own (linked without BrotliRegister.o; the brotli library itself stays inside): method id 4F71102 resolves to the
     plugin for encoding AND decoding, and the plugin finds the RFC's static dictionary in the host (BrotliGetDictionary of its 7z.so)."""
     if not os.path.exists(os.path.join(HOST, "7z_nobrotli.so")):
-        if os.path.isdir("/root/reference/CPP"):
-            subprocess.run(["bash", os.path.join(ROOT, "oracle", "build_ref_7z.sh"), HOST], check=True, capture_output=True, env=dict(os.environ, REF_ROOT="/root/reference"))
+        _build_host()
         if not os.path.exists(os.path.join(HOST, "7z_nobrotli.so")):
             pytest.skip("reference host without brotli not built (oracle/_ref/host7z/7z_nobrotli.so)")
     d = tmp_path_factory.mktemp("host7z_nobrotli")

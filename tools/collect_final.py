@@ -15,7 +15,7 @@ t = [f for f in sorted(os.listdir(G)) if f.startswith("tests")]
 open(os.path.join(P, "r%s_final_gpu_tests.md" % rnd), "w").write(head + ": `python -m pytest tests -m gpu -q`\n```\n" + "".join(l for l in rd(t[0]).splitlines(True) if not l.startswith("/opt/amdgpu")) + "```\n" + ("smoke: " + rd("smoke.log").strip().splitlines()[-1] + "\n" if rd("smoke.log").strip() else ""))
 # bench lines: the default one, then the three per-codec lines in the order they ran
 b = sorted([f for f in os.listdir(G) if re.match(r"bench\d+\.json", f)], key=lambda f: int(re.findall(r"\d+", f)[0]))
-names = ["the default `python bench.py` line (the metric: zstd-L3 on the 1 GB enwik9 stand-in, Fast-LZMA2-L5 on the Silesia stand-in in `flzma2_l5_silesia`, `real_data`, both CPU baselines)",
+names = ["the `python bench.py --full` line (the metric: zstd-L3 on the 1 GB enwik9 stand-in, Fast-LZMA2-L5 on the Silesia stand-in in `flzma2_l5_silesia`, `real_data`, both CPU baselines)",
          "C2: zstd level 3, 100 MB (`--codec zstd --bytes 100000000 --no-cpu-baseline`)", "C4 share: zstd level 19, 125 MB (`--codec zstd --level 19 --bytes 125000000 --no-cpu-baseline`)",
          "C5 share: brotli quality 6, 1 GB of web-text (`--codec brotli --no-cpu-baseline`)"]
 out = [head + ": bench lines", ""]
@@ -25,7 +25,7 @@ open(os.path.join(P, "r%s_final_bench_line.md" % rnd), "w").write("\n".join(out)
 # kernel stats
 ks = [f for f in sorted(os.listdir(G)) if f.startswith("kernel_stats")]
 if ks:
-    open(os.path.join(P, "r%s_final_metric_kernel_stats.md" % rnd), "w").write(head + ": rocprofv3 --kernel-trace --stats of `python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-decode-check` (both legs of the metric; 4 calls = 1 warm-up + 3 steps)\n\n" + rd(ks[0]))
+    open(os.path.join(P, "r%s_final_metric_kernel_stats.md" % rnd), "w").write(head + ": rocprofv3 --kernel-trace --stats of `python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-decode-check` (both legs of the metric; 4 calls = 1 warm-up + 3 steps)\n\n" + rd(ks[0]))
 # pmc
 pm = sorted([f for f in os.listdir(G) if re.match(r"pmc\d+\.md", f)], key=lambda f: int(re.findall(r"\d+", f)[0]))
 codecs = ["zstd", "flzma2", "brotli"][:len(pm)]

@@ -3,7 +3,7 @@
 # Outputs under gpurun_out/<tag>/; every step is bounded by its own timeout.  Steps:
 #   smoke                                   __graft_entry__.smoke()
 #   tests[:<pytest args>]                   python -m pytest -m gpu -q <args>      (default: the whole suite; "," separates args)
-#   bench[:<bench.py args>]                 one bench line -> bench<k>.json        (default: the metric)
+#   bench[:<bench.py args>]                 one bench.py --full line -> bench<k>.json (default: the metric)
 #   shard[:<Ns>]                            bench.py --shard-of <Ns>               (default 1,2,4,8; both legs of the metric)
 #   ratio:<codec>:<levels>:<corpora>:<MiB>[:<ENV=V,...>]   tools/gpu_ratio.py (sizes against the reference, decode check); env => hooks library
 #   prof[:<bench.py args>]                  rocprofv3 --kernel-trace --stats of the bench command -> kernel_stats<k>.md
@@ -19,7 +19,7 @@ for step in "$@"; do
   case $kind in
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -2 $OUT/smoke.log ;;
     tests) timeout 1500 python -m pytest ${args:-tests} -m gpu -q > $OUT/tests$k.log 2>&1; tail -5 $OUT/tests$k.log ;;
-    bench) timeout 1200 python bench.py $args > $OUT/bench$k.json 2> $OUT/bench$k.err; tail -2 $OUT/bench$k.err
+    bench) timeout 1200 python bench.py --full $args > $OUT/bench$k.json 2> $OUT/bench$k.err; tail -2 $OUT/bench$k.err
            python - <<PY
 import json
 try:
@@ -46,13 +46,13 @@ PY
            lib=""; [ -n "$envs" ] && lib="--lib 7-zip-zstd_amd/csrc/libgpucodec_hooks.so"
            env $(echo "$envs" | tr ',' ' ') timeout 900 python tools/gpu_ratio.py $lib --bytes $(( ${mib:-64} * 1024 * 1024 )) --codecs $codec --levels $levels --corpora $corpora > $OUT/ratio$k.jsonl 2> $OUT/ratio$k.err
            cut -c1-200 $OUT/ratio$k.jsonl; tail -2 $OUT/ratio$k.err ;;
-    prof)  R=$PWD; (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof$k -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-decode-check $args > $R/$OUT/bench_prof$k.json 2> $R/$OUT/prof$k.err)
+    prof)  R=$PWD; (cd "$TMPDIR" && timeout 900 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof$k -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-decode-check $args > $R/$OUT/bench_prof$k.json 2> $R/$OUT/prof$k.err)
            DB=$(find $OUT/prof$k -name '*.db' | head -1)
            [ -n "$DB" ] && python tools/rocpd_summary.py $DB > $OUT/kernel_stats$k.md && head -45 $OUT/kernel_stats$k.md
            rm -rf $OUT/prof$k ;;
     pmc)   rm -f $OUT/pmc$k.md
            for ctr in FETCH_SIZE WRITE_SIZE; do
-             timeout 600 rocprofv3 --pmc $ctr --kernel-trace -d $OUT/pmc_$ctr -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-decode-check $args > $OUT/pmc_$ctr.json 2> $OUT/pmc_$ctr.err
+             timeout 600 rocprofv3 --pmc $ctr --kernel-trace -d $OUT/pmc_$ctr -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-decode-check $args > $OUT/pmc_$ctr.json 2> $OUT/pmc_$ctr.err
              DB=$(find $OUT/pmc_$ctr -name '*.db' | head -1)
              if [ -n "$DB" ]; then echo "## $ctr" >> $OUT/pmc$k.md; python tools/rocpd_pmc.py $DB >> $OUT/pmc$k.md; echo >> $OUT/pmc$k.md; else echo "## $ctr: no result" >> $OUT/pmc$k.md; tail -3 $OUT/pmc_$ctr.err >> $OUT/pmc$k.md; fi
              rm -rf $OUT/pmc_$ctr
