@@ -111,23 +111,7 @@ struct gc_ctx {
     hipStream_t stream3;      // FLZMA2: range-coder stage
     hipEvent_t evPart[GC_MAX_PARTS][GC_PART_EVENTS];   // per input part: stage boundaries (see gc_flzma2_compress_device)
     uint32_t nParts;
-    uint32_t lazyDepth;       // W6: 1 = one-step lazy, 2 = lazy2 (set per call from codec + level)
-    uint32_t searchDepth;     // W5b: match links followed per position (0 = W5's two candidates only) -- by the starts of matches in tiles with long matches
-    uint32_t searchShallow;   // ... and everywhere else (gc_mf_deepen_kernel)
-    uint32_t shortPass;       // third finder pass with 4- / 3-byte keys; its merged records feed the price-based parse only
-    uint32_t farPass;         // second finder pass with 16- / 12-byte keys (longer matches), merged into the records by gain
     uint32_t optSeekTable, optBrotliPlain;   // gc_ctx_set_option
-    uint32_t mfFast;          // geometry of the windowed finder (gc_mf.h): 1 = 256 partitions / 8 KiB tiles, 0 = 1024 partitions / 16 KiB tiles
-    uint32_t priceParse;      // W5s + W7: price-based parse on top of the greedy one (gc_lz_price.hip)
-    uint32_t priceMinLen, priceLitCtx;        // its shortest match and literal context bits (LZMA: 2, 7; zstd: 3, 0)
-    int lastCodecHint;        // codec of the call being enqueued (0 zstd, 1 flzma2, 2 brotli): which W7L kernels the finder launches
-    uint32_t allLengths;      // W7L (zstd): every length of a candidate is an edge
-    uint32_t smallWin2k;      // W7L: windows of 2 KiB in calls of <= 1 024 blocks (launch_finder_part)
-    uint32_t shortPlain;      // overlapping frames: the pass with 4- / 3-byte keys runs over frames that tile the input (launch_finder_part)
-    uint32_t farPass2;        // one more pass of the far kind with keys of 32 / 24 bytes (gc_lz_window.hip MF_FAR2)
-    uint32_t laneParse;       // the price-based parse is W7L (a lane per window, repeat distances at every node) rather than W7
-    uint32_t ringGeom;        // W6r: threads per block (16 per sub-block)
-    uint32_t ringParse;       // W6r (brotli qualities 5-6): the parse walks the records in order with the last four distances as candidates; the value = shortest copy at a ring distance, 0 = W6
     uint32_t dbgFrameBlocks, dbgPartFrames;   // test hooks (env GC_FRAME_BLOCKS / GC_PART_FRAMES): small frames / parts so that
                                               // the multi-frame and multi-part paths can be exercised on small inputs
     hipEvent_t ev[8];         // 0 lz start, 1 lz end, 2 huf end, 3 seq start, 4 seq end, 5 plan start, 6 plan end, 7 emit end
@@ -184,6 +168,7 @@ extern "C" int gc_test_hooks_enabled(void) { return 1; }
 static inline bool gc_env_u32(const char*, uint32_t, uint32_t, uint32_t*) { return false; }
 extern "C" int gc_test_hooks_enabled(void) { return 0; }
 #endif
+static uint32_t dbg_frame_blocks(void) { uint32_t v = 0; gc_env_u32("GC_FRAME_BLOCKS", 1u, GC_MF_MAX_FRAME_BLOCKS, &v); return v; }      // test hook: small frames (0 = off)
 
 #define HIPCHK(ctx, call)                                                                       \
     do { hipError_t e_ = (call);                                                                \
@@ -235,9 +220,8 @@ extern "C" int gc_ctx_create(gc_ctx** out, int device)
     if (rc == GC_OK && (hipMalloc((void**)&c->mfTicket, GC_MAX_PARTS * 16u * sizeof(uint32_t)) != hipSuccess || hipMemsetAsync(c->mfTicket, 0, GC_MAX_PARTS * 16u * sizeof(uint32_t), c->stream) != hipSuccess)) rc = GC_ERR_NOMEM;
     if (rc == GC_OK && (hipMalloc((void**)&c->result, 16) != hipSuccess || hipHostMalloc((void**)&c->hostResult, 16 + GC_MAX_PARTS * 16u * sizeof(uint32_t)) != hipSuccess)) rc = GC_ERR_NOMEM;      // (+ a copy of the ticket / watchdog words)
     if (rc != GC_OK) { ctx_release(c); return rc; }
-    c->dbgFrameBlocks = 0; c->dbgPartFrames = 0;
-    gc_env_u32("GC_FRAME_BLOCKS", 1u, GC_MF_MAX_FRAME_BLOCKS, &c->dbgFrameBlocks);      // test hooks: small frames / parts
-    gc_env_u32("GC_PART_FRAMES", 1u, 1u << 20, &c->dbgPartFrames);
+    c->dbgFrameBlocks = dbg_frame_blocks(); c->dbgPartFrames = 0;
+    gc_env_u32("GC_PART_FRAMES", 1u, 1u << 20, &c->dbgPartFrames);                      // test hook: small parts
     *out = c;
     return GC_OK;
 }
@@ -327,6 +311,177 @@ static int ensure_workspace(gc_ctx* c, uint32_t nBlocks)
     return GC_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ codec level -> finder and parse settings
+// What the match finder (W1..W5b) and the parses (W5s, W6, W6r, W7, W7L) run for ONE call: zstd_plan / flzma2_plan / brotli_plan fill it from
+// the level, with_hooks applies the test hooks, and the compress path hands it to the finder.  The frames the finder runs over: lz_frame_arg.
+struct GcLzPlan {
+    int codec = GC_CODEC_ZSTD;      // which W7L kernels the finder launches
+    uint32_t lazyDepth = 1u;        // W6: 1 = one-step lazy, 2 = lazy2
+    uint32_t mfFast = 0u;           // geometry of the windowed finder (gc_mf.h): 1 = 256 partitions / 8 KiB tiles, 0 = 1024 partitions / 16 KiB tiles
+    uint32_t searchDepth = 0u, searchShallow = 0u;    // W5b: match links followed per position by the starts of matches in tiles with long matches / everywhere else (gc_mf_deepen_kernel; 0 = W5's two candidates only)
+    uint32_t farPass = 0u;          // second finder pass with 16- / 12-byte keys (longer matches), merged into the records by gain
+    uint32_t farPass2 = 0u;         // one more pass of the far kind with keys of 32 / 24 bytes (gc_lz_window.hip MF_FAR2)
+    uint32_t shortPass = 0u;        // third finder pass with 4- / 3-byte keys; its merged records feed the price-based parse only
+    uint32_t shortPlain = 0u;       // overlapping frames: the pass with 4- / 3-byte keys runs over frames that tile the input
+    uint32_t priceParse = 0u;       // W5s + W7: price-based parse on top of the greedy one (gc_lz_price.hip)
+    uint32_t priceMinLen = 3u, priceLitCtx = 0u;      // its shortest match and literal context bits (LZMA: 2, 7; zstd: 3, 0)
+    uint32_t laneDp = 0u;           // the price-based parse: 0 = W7 (a wave per window), 1 = W7L (gc_lz_dpl.hip: a lane per window, repeat distances at every node) everywhere, 2 = phase A in W7L, phase B per block in W7 or W7L by what phase A's paths did (gc_mf.h GC_DPS_RICH)
+    uint32_t dpPhases = 2u;         // W7 / W7L: 2 = phase A (a sample of the windows under optimistic prices) then B (prices from A's paths), 1 = B alone on W6's prices
+    uint32_t smallWin2k = 0u;       // W7L windows of 2 KiB: 0 never, 1 in parts of <= 1 024 blocks (launch_finder_part), 2 always
+    uint32_t allLengths = 0u;       // W7L (zstd): every length of a candidate is an edge
+    uint32_t ringParse = 0u;        // W6r (brotli qualities 5-6): the parse walks the records in order with the last four distances as candidates; the value = shortest copy at a ring distance, 0 = W6
+    uint32_t ringGeom = 256u;       // W6r: threads per block (16 per sub-block)
+};
+
+// zstd level -> blocks per frame.  Every level runs the windowed finder over 8 MiB frames (round 3).  Levels 1-2 used the block-local finder before -- a 128 KiB window against the
+// 512 KiB / 1 MiB windows of the reference's levels 1 / 2 (clevels.h:26-27): 1.026 x its level 1 on text, 1.085 x its level 2 (run r03_levels).
+// The block-local kernel K1 still serves inputs of one block.
+static uint32_t zstd_frame_blocks(int level) { return level >= 18 ? GC_MF_WIDE_MAX_FRAME_BLOCKS : GC_MF_MAX_FRAME_BLOCKS; }       // (round 6: 16 MiB windows at 18-22 -- the reference: windowLog 23 at 18-19, 25-27 at 20-22, clevels.h:46-50)
+// Levels 16-22: the finder's frames overlap (gc_mf.h "Overlapping frames") inside groups that are the zstd frames.  The reference: windowLog 22 at level 16-17, 23 at 18-19,
+// 25 / 26 / 27 at 20 / 21 / 22 (clevels.h:44-50), one frame, ZSTDMT jobs of four windows overlapping by one (zstdmt_compress.c:741-747).  Here the window stays 8 MiB
+// (23-bit positions); what the levels choose is how much of it a position is sure to have behind it: stride 4 MiB = 4-8 MiB of history at 16-19, stride 2 MiB = 6-8 MiB at
+// 20-22 (each halving of the stride lists and links every position once more: W1..W4 of the three passes).
+static uint32_t zstd_group_blocks(int level) { return level >= 16 ? 4u * GC_MF_MAX_FRAME_BLOCKS : GC_MF_MAX_FRAME_BLOCKS; }     // 32 MiB zstd frames (= shard grain) / 8 MiB
+static uint32_t zstd_stride_blocks(int level) { return (level == 18 || level == 19) ? GC_MF_MAX_FRAME_BLOCKS : GC_MF_MAX_FRAME_BLOCKS / 2u; }      // a position is sure of 4 MiB of history at 16-17 (8 MiB windows every 4 MiB), of 8 MiB -- the reference's whole window -- at 18-19 (16 MiB windows every 8 MiB), of 12 MiB at 20-22 (every 4 MiB; round 5: 8 MiB windows every 2 MiB)
+
+static GcLzPlan zstd_plan(int level)
+{
+    GcLzPlan p; p.codec = GC_CODEC_ZSTD;
+    p.lazyDepth = level >= 6 ? 2u : 1u;          // the reference's lazy2 begins at level 8 of its table; deeper look-ahead from 6 here
+    p.mfFast = level <= 6 ? 1u : 0u;             // no far pass below level 7: the fast geometry (gc_mf.h)
+    // (Listing half of the positions, chosen by content, was measured at level 3 in rounds 2 and 5 -- 1 GB of text 43.2 -> 39.0 ms for +3.5-4.5 % size, real sources 0.949 -> 1.158 x
+    //  the reference -- and again in round 6's lab with the catch-up in place (tools/zstd_parse_lab.c policy 4: shared objects +10 %): not taken, its kernels are gone.)
+    p.searchDepth = level < 6 ? 0u : (level < 10 ? 2u : (level < 16 ? 4u : (level < 18 ? 8u : 16u)));      // the reference's searchLog grows the same way (clevels.h:25-47)
+    p.searchShallow = p.searchDepth < 2u ? p.searchDepth : 2u;
+    p.farPass = level >= 5 ? 1u : 0u;            // where the reference searches chains / trees (lazy2 and up).  Measured (run 29, 32 MiB): level 9
+                                                 // 1.027 -> 0.984 x the reference on text, level 12 1.040 -> 1.001 x.  Round 6: from level 5 (was 7) -- the reference's greedy / lazy
+                                                 // strategies at 5-6 walk hash chains (zstd_lazy.c:667, searchLog 3: clevels.h:33-34), and on real sources the first pass alone was
+                                                 // 1.135 x its level 5 and 1.136 x its level 6 (32 / 8 MiB, run s4: nobody had looked); with the two far passes 0.932 / 0.984 (emulator, 8 MiB)
+    p.shortPass = level >= 5 ? 1u : 0u;          // the reference's btopt strategies search 3-byte matches (minMatch 3, clevels.h:44-47); from level 10 since round 3, from level 7 since round 6, see priceParse
+    p.allLengths = level >= 18 ? 1u : 0u;        // levels 16-17 (the reference: btopt / btultra with searchLog 5) keep the sparse lengths and the two far passes; 18-22 (btultra / btultra2, searchLog 6-9) price every length
+    p.farPass2 = (level >= 5 && level != 16 && level != 17) ? 1u : 0u;      // keys of 32 / 24 bytes where the reference searches chains / trees for the LONGEST match: real sources, emulator, 8 MiB:
+                                                                            // level 9 1.118 -> 1.050 x the reference, level 19 1.115 -> 1.097
+    p.laneDp = level >= 16 ? 2u : 0u;            // the reference's btopt .. btultra2 (clevels.h:44-50) price its three repeat offsets at every position; real sources / binaries at level 19
+                                                 // (emulator, 4 MiB): 1.109 / 1.124 x the reference with W7, 1.081 / 1.075 with W7L.  Levels 10-15 (the reference: lazy2 / btlazy2) keep W7.
+                                                 // W7L by block: text repeats an offset in 1 % of its sequences and sources / binaries in 8-46 %: 125 MB of text at level 19
+                                                 // 3.78 -> 4.75 GB/s (run r4s), the sizes of W7L where it matters
+    p.priceMinLen = 3u; p.priceLitCtx = 0u;      // zstd: matches of >= 3 bytes, literals without context (one Huffman table per block)
+    p.priceParse = level >= 5 ? 1u : 0u;         // the reference's btopt / btultra strategies start at level 16 (clevels.h:44-47), its levels 10-15 are lazy2 / btlazy2 over deep
+                                                 // chains and trees; the greedy / lazy2 parse over this finder's 3-6 candidates was 1.03 x them on lz-7zip (levels 10 and 12, run r03_z12),
+                                                 // the price-based parse 0.98 -- so it started at level 10 in round 3.  Round 6: from level 7, where the far passes start.  The reference's
+                                                 // lazy2 at 7-9 picks the longest of 16-32 tagged row candidates (zstd_lazy.c:1141); the lazy parse over this finder's gain-merged record was
+                                                 // 1.058-1.062 x it on real shared objects (level 7 LARGER than level 5: a far match that wins by `4 len - log2 offset` is often dearer than the
+                                                 // near one it replaces); with the short pass + the price-based parse 1.026 / 1.028 (emulator, 8 MiB; real sources 1.038 -> 0.978, text 0.942 -> 0.909).
+                                                 // And from level 5 once the far passes start there: levels 5 / 6 on shared objects 1.043 / 1.048 with the lazy parse over the merged records, 1.014 / 1.017 with
+                                                 // this one (real sources 0.891).  Levels 5-12 now differ in the geometry (5-6: the fast one), the links followed (0 / 2 / 4) and nothing else
+    return p;
+}
+
+// FLZMA2 level -> blocks per match-finder frame.  Every level runs the windowed finder over 8 MiB frames (round 3; levels 1-2 used the block-local
+// finder before: a 128 KiB window against the reference's 1-2 MiB dictionaries, fl2_compress.c:52-63, was 12-24 % behind it, run r03_levels).
+static uint32_t flzma2_frame_blocks(int level) { return level >= 7 ? GC_MF_WIDE_MAX_FRAME_BLOCKS : GC_MF_MAX_FRAME_BLOCKS; }     // (round 6: 16 MiB windows at 7-9 -- the reference: dictionaries of 32 / 64 / 64 MiB, fl2_compress.c:74-86)
+// Levels 7-9 (the reference: dictionaries of 64 / 64 / 128 MiB, fl2_compress.c:59-62): overlapping finder frames (gc_mf.h) in groups of 64 MiB, stride 4 MiB at 7, 2 MiB at 8-9
+// (a position is sure of 4 / 6 MiB of history; the window itself stays 8 MiB: 23-bit positions).  Levels 1-6: frames that tile the input.
+// Levels 5-6 (round 5; the reference: 16 / 32 MiB dictionaries): groups of 16 MiB, stride 4 MiB -- real shared objects, 32 MiB at level 5 on the emulator: 1.0186 -> 1.0148 x the reference
+static uint32_t flzma2_group_blocks(int level) { return level >= 7 ? 8u * GC_MF_MAX_FRAME_BLOCKS : (level >= 5 ? 2u * GC_MF_MAX_FRAME_BLOCKS : GC_MF_MAX_FRAME_BLOCKS); }
+static uint32_t flzma2_stride_blocks(int level) { return level >= 8 ? GC_MF_MAX_FRAME_BLOCKS / 2u : (level >= 7 ? GC_MF_MAX_FRAME_BLOCKS : GC_MF_MAX_FRAME_BLOCKS / 2u); }      // 5-6: 4 MiB (8 MiB windows); 7: 8 MiB, 8-9: 4 MiB (16 MiB windows: 8-16 / 12-16 MiB of history)
+
+static GcLzPlan flzma2_plan(int level)
+{
+    GcLzPlan p; p.codec = GC_CODEC_FLZMA2;
+    p.lazyDepth = level >= 5 ? 2u : 1u; p.mfFast = 0u; p.searchShallow = level >= 5 ? 2u : 0u;
+    p.searchDepth = level >= 5 ? (level >= 8 ? 16u : 12u) : 0u;    // links followed where a tile has long matches, by the positions that start one (two links elsewhere: gc_mf_deepen_kernel).
+                                                                    // Real source text (64 MiB): two links everywhere 1.030 x the reference, six everywhere 1.017 (run r03_depth)
+    p.farPass = level >= 3 ? 1u : 0u;            // the reference's match table resolves to depth 42 at level 5 (fl2_compress.c:37-104);
+                                                 // level 3 (run 30x, 32 MiB): 1.071 -> 1.026 x the reference on text
+    p.shortPass = level >= 3 ? 1u : 0u;          // ... and holds the nearest match of >= 2 bytes for every position
+    p.shortPlain = level < 7 ? 1u : 0u;          // (the levels that are not after speed keep the overlap: the generator of lz-7zip copies 3-4 bytes from anywhere in its window, 32 MiB at level 7: +0.26 % without)
+    p.farPass2 = level >= 7 ? 1u : 0u;           // keys of 32 / 24 bytes (gc_lz_window.hip MF_FAR2) at the ultra levels
+    p.laneDp = 1u;                               // W7L everywhere: LZMA with the four repeat distances at every node.  (Per block as zstd does: on the Silesia stand-in half of the blocks
+                                                 // sit right at the threshold, and a W7L launch takes as long for a few blocks as for all of them -- it ends with its slowest wave, and all of
+                                                 // its waves fit the device at once -- so the two kernels' times add up: 40 -> 49 ms.)
+    // Windows of 2 KiB (one block per wave) where the 4 KiB ones leave the device half empty: W7L takes as long as ONE wave needs for its window, whatever the number of waves,
+    // as long as they are all resident (1 024 groups of 64 windows); a call of <= 1 024 blocks (128 MiB) has at most 512 groups of 4 KiB windows.  Round 4 measured 32 MiB
+    // 23.5 -> 13.6 ms and 128 MiB 25.4 -> 15.7 ms for +0.02 % (the Silesia stand-in) ... +0.36 % (shared objects) and left it off because the size bars sat at the band's edge;
+    // round 5 (merged model segments, overlapping frames) moved them: on at levels 5-6.
+    p.smallWin2k = (level == 5 || level == 6) ? 1u : 0u;
+    p.priceMinLen = 2u; p.priceLitCtx = 7u;
+    p.priceParse = level >= 3 ? 1u : 0u;         // the reference's FL2_opt strategy starts at level 3 of its 7-Zip table (fl2_compress.c:52-63); round 3 (run r03_fl2ab): level 3 with
+                                                 // the greedy parse was 1.038 x the reference on silesia-like, with the price-based parse 1.002
+    return p;
+}
+
+// BROTLI: chunk = 1 MiB x level as in brotli-mt (C/zstdmt/brotli-mt_compress.c:115-118), in 128 KiB blocks
+static uint32_t brotli_blocks_per_chunk(int level) { if (level < 1) level = 1; if (level > 11) level = 11; return (uint32_t)level * 8u; }
+
+static GcLzPlan brotli_plan(int level)
+{
+    GcLzPlan p; p.codec = GC_CODEC_BROTLI;
+    p.lazyDepth = level >= 5 ? 2u : 1u;          // W6 looks two positions ahead from quality 5 (round 6, emulator, 4 MiB at quality 6: web-text 0.960 -> 0.950 x the reference;
+                                                 // it was 7).  W6r keeps one position (two: shared objects 1.035 -> 1.039)
+    p.mfFast = level <= 6 ? 1u : 0u;             // (qualities 5-6 run the far pass on the fast geometry: 0.97-0.99 x the reference at 15 % less time than on the wide one)
+    // W5b from quality 7: four links (eight from quality 10) for the starts of matches in tiles with long matches, two elsewhere.  Quality 5 stays without it (round 3 measured
+    // quality 6 with (8, 0) (run r03_q3): sources 1.084 -> 1.068 x the reference and the Python library 1.024 -> 1.015, but web-text -- config C5's data, whose boilerplate
+    // makes most tiles "long" -- 16.6 -> 9.4 GB/s for 0.3 % of its size
+    // Quality 6 follows ONE link everywhere since round 4 (run r4brd / r4brd3, 64 MiB per corpus, web-text 500 MB): real Python library 1.024 -> 1.015 x the reference (inside the
+    // band), real sources 1.084 -> 1.069, shared objects 1.106 -> 1.101, web-text 17.0 -> 14.5 GB/s (W5b 5.0 ms per 500 MB).  One link for the starts of matches only:
+    // 1.020 / 1.076 / 1.104 at 15.0 GB/s; two links: 1.010 / 1.062 / 1.099 at 12.9; four (starts only beyond two): 1.009 / 1.059 / 1.098 at 11.4.  Quality 5 stays without.
+    p.searchDepth = level >= 7 ? (level >= 10 ? 8u : 4u) : (level == 6 ? 1u : 0u); p.searchShallow = p.searchDepth < 2u ? p.searchDepth : 2u;
+    p.farPass = level >= 5 ? 1u : 0u;            // longer matches stand in for the context modelling / block splitting B1 lacks
+    p.ringParse = level >= 5 ? (2u | (8u << 8) | (4u << 16) | (16u << 24)) : 0u;
+    p.laneDp = level >= 7 ? 2u : 0u;             // qualities 7-11: W7L with the ring's first entries as its repeat distances, per block where phase A's paths repeat.  Qualities 8-11 run
+                                                 // zstd's W7L kernels since round 6: the parse's last distances at every node, which B1 then codes as ring entries; 32 MiB at quality 9:
+                                                 // shared objects 1.023 -> 0.980 x the reference, real sources 1.092 -> 1.038, text / web-text / lz-7zip as before -- phase B goes to W7 there
+    p.priceMinLen = 3u; p.priceLitCtx = 0u;      // copies of >= 3 bytes (a 2-byte copy at a fresh distance never pays in brotli), one literal code per meta-block
+    p.priceParse = level >= 7 ? 1u : 0u;         // (quality 7 since round 6 -- emulator, 2 MiB, with W7L: real sources 1.018 -> 0.980 x the reference, shared objects 1.040 -> 1.026, text 0.963 -> 0.939.)
+                                                 // The reference parses greedily up to quality 9 (zopfli from 10).  Measured at quality 6
+                                                 // (run 28, 64 MiB per corpus): greedy + far pass 0.979-1.002 x the reference at 16.6 GB/s,
+                                                 // price-based parse without far pass 0.983-1.012 x at 11.1 GB/s, both 0.93-0.98 x at 9.4 GB/s
+    return p;
+}
+
+// Test hooks on the finder and the parses, applied to the level's settings before anything is derived from them
+static GcLzPlan with_hooks(GcLzPlan p)
+{
+    gc_env_u32("GC_PRICE_PARSE", 0u, 1u, &p.priceParse);                // 0 = greedy parse only
+    gc_env_u32("GC_FAR2_PASS", 0u, 1u, &p.farPass2);
+    { uint32_t v = 0; if (gc_env_u32("GC_DPL", 0u, 2u, &v) && !(p.codec == GC_CODEC_BROTLI && p.laneDp == 0u)) p.laneDp = v; }     // (brotli below quality 7: W7 whatever the hook)
+    { uint32_t v = 0; if (gc_env_u32("GC_DPL_WIN2K", 0u, 1u, &v)) p.smallWin2k = v ? 2u : 0u; }
+    gc_env_u32("GC_DP_PHASES", 1u, 2u, &p.dpPhases);
+    if (p.codec == GC_CODEC_BROTLI) gc_env_u32("GC_BR_RING", 0u, 0xFFFFFFFFu, &p.ringParse);
+    { uint32_t g = 0; if (p.codec == GC_CODEC_BROTLI && gc_env_u32("GC_BR_RING_GEOM", 64u, 256u, &g) && (g & 63u) == 0u) p.ringGeom = g; }     // 64 / 128 / 256 threads = 4 / 8 / 16 sub-blocks
+    return p;
+}
+
+// The finder's frame argument for a call of nBlocks blocks: F, or F | S << 8 | C << 16 where frames overlap (gc_mf.h "Overlapping frames").  zstd / FLZMA2:
+// the level's frames (dbgFrameBlocks != 0: test hook GC_FRAME_BLOCKS, small frames), overlapping inside groups -- the zstd frames, the FLZMA2 parts' unit -- where the
+// level or the hooks GC_MF_GROUP / GC_MF_STRIDE say so.  BROTLI: frames that tile the brotli-mt chunk.  A short input is one frame.  gc_codec_grain passes
+// nBlocks = UINT32_MAX: one function, so that a shard's frames are the whole input's.
+static uint32_t lz_frame_arg(int codec, int level, uint32_t nBlocks, uint32_t dbgFrameBlocks)
+{
+    if (codec == GC_CODEC_BROTLI) {
+        // quality -> blocks per frame.  Quality 0: block-local finder.  Above (from quality 1 since round 3: 1.04 x the reference before): the windowed finder over frames that
+        // tile the chunk exactly (a copy must not reach into the previous chunk: every chunk is a brotli stream of its own), the whole
+        // chunk when it is <= 8 MiB (qualities 3-8), half of it above (72/80/88 blocks -> 36/40/44).
+        const uint32_t bpc = brotli_blocks_per_chunk(level);
+        const uint32_t cap = level >= 7 ? GC_MF_WIDE_MAX_FRAME_BLOCKS : GC_MF_MAX_FRAME_BLOCKS;   // (qualities >= 7 run the wide geometry: 16 MiB of positions, so the 9 / 10 / 11 MiB chunks of qualities 9-11 are ONE frame since round 6)
+        const uint32_t f = level <= 0 ? 1u : (bpc <= cap ? bpc : bpc / 2u);
+        return f < nBlocks ? f : nBlocks;
+    }
+    const bool z = codec == GC_CODEC_ZSTD;
+    const uint32_t fLevel = z ? zstd_frame_blocks(level) : flzma2_frame_blocks(level);
+    uint32_t f = (fLevel > 1u && dbgFrameBlocks) ? dbgFrameBlocks : fLevel;
+    if (f > nBlocks) f = nBlocks;
+    uint32_t grp = z ? zstd_group_blocks(level) : flzma2_group_blocks(level);
+    const bool grpHook = gc_env_u32("GC_MF_GROUP", 1u, 65535u, &grp);                              // test hook: blocks per group
+    if (grp > f && (f == fLevel || grpHook) && nBlocks > f) {
+        uint32_t stride = z ? zstd_stride_blocks(level) : flzma2_stride_blocks(level);
+        gc_env_u32("GC_MF_STRIDE", 1u, GC_MF_MAX_FRAME_BLOCKS, &stride);                            // test hook (blocks; 64 = no overlap)
+        if (stride < f && (f % stride) == 0u && ((grp - f) % stride) == 0u) return GC_MF_GEOM_ARG(f, stride, grp);
+    }
+    return f;
+}
+
 // ------------------------------------------------------------------------------------------------ match finder dispatch
 // frameBlocks == 1: K1, the block-local finder (hash tables in LDS, matches stay inside the 128 KiB block).
 // frameBlocks  > 1: W1..W6, the windowed finder (gc_lz_window.hip): matches reach back to the start of the frame.
@@ -361,17 +516,17 @@ static uint32_t mf_auto_parts(size_t n, uint32_t frameArg)
     size_t parts = (nGroups + perPart - 1u) / perPart;
     return (uint32_t)(parts < 1u ? 1u : (parts > GC_MAX_PARTS ? GC_MAX_PARTS : parts));
 }
-static int ensure_finder_workspace(gc_ctx* c, size_t n, uint32_t frameBlocks, size_t maxPartBytes = 0 /* bytes of the largest part; 0: one part */)
+static int ensure_finder_workspace(gc_ctx* c, const GcLzPlan& plan, size_t n, uint32_t frameBlocks, size_t maxPartBytes = 0 /* bytes of the largest part; 0: one part */)
 {
     if (MF_F(frameBlocks) <= 1u) return GC_OK;                  // (frameBlocks: F, or F | S << 8 | C << 16 -- overlapping frames, gc_mf.h)
-    const GcMfGeom g = gc_mf_geom(n, frameBlocks, c->mfFast != 0u);
-    const GcMfGeom gp = gc_mf_geom(maxPartBytes && maxPartBytes < n ? maxPartBytes : n, frameBlocks, c->mfFast != 0u);
+    const GcMfGeom g = gc_mf_geom(n, frameBlocks, plan.mfFast != 0u);
+    const GcMfGeom gp = gc_mf_geom(maxPartBytes && maxPartBytes < n ? maxPartBytes : n, frameBlocks, plan.mfFast != 0u);
     const size_t needCnt = gp.cntWords * sizeof(uint32_t), needEnt = (size_t)gp.nFrames * gp.frameBytes * sizeof(GcMfEntry);
     const size_t needRec = (size_t)g.nBlocks * GC_ZSTD_BLOCK_MAX * sizeof(uint32_t);
     const size_t needPrice = (size_t)g.nBlocks * GC_PRICE_WORDS * sizeof(uint16_t);
     const size_t needTileWord = ((size_t)g.nTiles + 64u) * sizeof(uint32_t);
-    if (needTileWord > c->mfTileWordCap || needCnt > c->mfCntCap || needEnt > c->mfEntCap || needEnt > c->mfEnt2Cap || needRec > c->mfRecCap || ((c->searchDepth || c->shortPass) && (needRec > c->mfRec2Cap || needRec / 32u + 64u > c->mfChangedCap)) ||
-        (c->priceParse && (needRec / 2u > c->mfRec3Cap || needRec > c->mfDpCap || needPrice > c->mfPriceCap || (size_t)g.nBlocks * 128u > c->mfWinCostCap || (size_t)g.nBlocks * GC_DPS_WORDS * 4u > c->mfDpStatCap || needRec / 4u > c->mfLitPriceCap))) {
+    if (needTileWord > c->mfTileWordCap || needCnt > c->mfCntCap || needEnt > c->mfEntCap || needEnt > c->mfEnt2Cap || needRec > c->mfRecCap || ((plan.searchDepth || plan.shortPass) && (needRec > c->mfRec2Cap || needRec / 32u + 64u > c->mfChangedCap)) ||
+        (plan.priceParse && (needRec / 2u > c->mfRec3Cap || needRec > c->mfDpCap || needPrice > c->mfPriceCap || (size_t)g.nBlocks * 128u > c->mfWinCostCap || (size_t)g.nBlocks * GC_DPS_WORDS * 4u > c->mfDpStatCap || needRec / 4u > c->mfLitPriceCap))) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         int rc;
         if ((rc = mf_grow(c, (void**)&c->mfTileWord, &c->mfTileWordCap, needTileWord, "tile counts")) != GC_OK) return rc;
@@ -379,9 +534,9 @@ static int ensure_finder_workspace(gc_ctx* c, size_t n, uint32_t frameBlocks, si
         if ((rc = mf_grow(c, (void**)&c->mfEnt, &c->mfEntCap, needEnt, "entries")) != GC_OK) return rc;
         if ((rc = mf_grow(c, (void**)&c->mfEnt2, &c->mfEnt2Cap, needEnt, "linked entries")) != GC_OK) return rc;
         if ((rc = mf_grow(c, (void**)&c->mfRec, &c->mfRecCap, needRec, "records")) != GC_OK) return rc;
-        if ((c->searchDepth || c->shortPass) && (rc = mf_grow(c, (void**)&c->mfRec2, &c->mfRec2Cap, needRec, "deepened records")) != GC_OK) return rc;
-        if ((c->searchDepth || c->shortPass) && (rc = mf_grow(c, (void**)&c->mfChanged, &c->mfChangedCap, needRec / 32u + 64u, "changed-record bitmap")) != GC_OK) return rc;
-        if (c->priceParse) {
+        if ((plan.searchDepth || plan.shortPass) && (rc = mf_grow(c, (void**)&c->mfRec2, &c->mfRec2Cap, needRec, "deepened records")) != GC_OK) return rc;
+        if ((plan.searchDepth || plan.shortPass) && (rc = mf_grow(c, (void**)&c->mfChanged, &c->mfChangedCap, needRec / 32u + 64u, "changed-record bitmap")) != GC_OK) return rc;
+        if (plan.priceParse) {
             if ((rc = mf_grow(c, (void**)&c->mfRec3, &c->mfRec3Cap, needRec / 2u, "short candidates")) != GC_OK) return rc;
             if ((rc = mf_grow(c, (void**)&c->mfDp, &c->mfDpCap, needRec, "price-parse records")) != GC_OK) return rc;
             if ((rc = mf_grow(c, (void**)&c->mfPrice, &c->mfPriceCap, needPrice, "price tables")) != GC_OK) return rc;
@@ -395,7 +550,7 @@ static int ensure_finder_workspace(gc_ctx* c, size_t n, uint32_t frameBlocks, si
 
 // Match finder for one part of the input: `src` / `n` are the part, blk0 its first block (a multiple of frameBlocks: parts are
 // whole frames, so everything inside is relative to the part and only the workspace pointers are offset).
-static int launch_finder_part(gc_ctx* c, hipStream_t st, uint32_t part, const uint8_t* src, size_t n, uint32_t frameArg /* F, or F | S << 8 | C << 16: overlapping frames (gc_mf.h) */, uint32_t blk0, unsigned long long* prof)
+static int launch_finder_part(gc_ctx* c, const GcLzPlan& plan, hipStream_t st, uint32_t part, const uint8_t* src, size_t n, uint32_t frameArg /* F, or F | S << 8 | C << 16: overlapping frames (gc_mf.h) */, uint32_t blk0, unsigned long long* prof)
 {
     const uint32_t frameBlocks = frameArg;                           // what W1..W5b take (they decode it: mf_tile)
     const uint32_t groupBlocks = MF_C(frameArg);                     // what the stages behind the finder call a frame: matches reach back to the start of the GROUP
@@ -407,19 +562,19 @@ static int launch_finder_part(gc_ctx* c, hipStream_t st, uint32_t part, const ui
         GC_LAUNCH(gc_zstd_lz_kernel, nBlocks, 1024, st, src, (uint64_t)n, seqRaw, lit, meta, prof);
         return GC_OK;
     }
-    const GcMfGeom g = gc_mf_geom(n, frameBlocks, c->mfFast != 0u);
+    const GcMfGeom g = gc_mf_geom(n, frameBlocks, plan.mfFast != 0u);
     const uint32_t frame0 = (blk0 / groupBlocks) * MF_FPG(frameArg);       // (parts are whole groups)
     uint32_t* cnt = c->mfCnt;                                              // count table and entry lists: every part from their start (ensure_finder_workspace)
     GcMfEntry* ent = c->mfEnt;
     GcMfEntry* ent2 = c->mfEnt2;
     uint32_t* rec = c->mfRec + (size_t)blk0 * GC_ZSTD_BLOCK_MAX;
     const uint32_t perT = gc_xcd_per(g.nTiles), perB = gc_xcd_per(nBlocks);
-    const bool fast = c->mfFast != 0u;
+    const bool fast = plan.mfFast != 0u;
     const uint32_t nParts = 1u << g.partLog;
 #define MFSEL(k) (fast ? k##_p8 : k)          // the kernel of this geometry
     // W4 is a persistent launch: one-wave workgroups, six per CU (24 KiB of LDS each), fed from a ticket counter (one counter per launch and part)
     uint32_t linkLaunch = 0;
-    uint32_t linkWpc = 6u; gc_env_u32("GC_LINK_WPC", 1u, 32u, &linkWpc);         // test hook: one-wave workgroups per CU
+    const uint32_t linkWpc = 6u;
     const uint32_t nLists = g.nFrames * nParts, linkGrid = nLists * GC_MF_LINK_SEGS < c->nCU * linkWpc ? nLists * GC_MF_LINK_SEGS : c->nCU * linkWpc;
     HIPCHK(c, hipMemsetAsync(c->mfTicket + part * 16u, 0, 16u * sizeof(uint32_t), st));      // words 0..3: W4's launches, 8..15: the fused kernel's XCD classes
 #define MF_LINK(cnt_, ent_, ent2_) do { uint32_t* ticket_ = c->mfTicket + part * 16u + linkLaunch++; \
@@ -428,7 +583,7 @@ static int launch_finder_part(gc_ctx* c, hipStream_t st, uint32_t part, const ui
     HIPCHK(c, hipEventRecord(ev[0], st));
     // W5s reads nothing but the input: it runs beside the finder's passes on the context's second stream (round 5; it was 1.5 ms of the main stream's chain per 212 MB).  stream2 is
     // also where the stages behind the finder run, later in the same call: stream order keeps them apart.
-    const bool shortBeside = c->priceParse && st == c->stream;
+    const bool shortBeside = plan.priceParse && st == c->stream;
     if (shortBeside) {
         HIPCHK(c, hipEventRecord(c->evShort[part], st)); HIPCHK(c, hipStreamWaitEvent(c->stream2, c->evShort[part], 0));        // (the input and the workspace are ready where `st` stands now)
         const uint32_t nChunkWg = (uint32_t)(((n + 2047u) / 2048u + 3u) / 4u), perC = gc_xcd_per(nChunkWg);
@@ -444,16 +599,14 @@ static int launch_finder_part(gc_ctx* c, hipStream_t st, uint32_t part, const ui
     MF_LINK(cnt, ent, ent2);
     HIPCHK(c, hipEventRecord(ev[4], st));
     // the levels that parse the first pass's records as they are: verify + parse in one kernel, the records stay in LDS (W5 + W6 fused)
-    uint32_t fused = (!c->farPass && !c->farPass2 && !c->searchDepth && !c->priceParse && !c->shortPass) ? 1u : 0u;
-    gc_env_u32("GC_FUSED_PARSE", 0u, 1u, &fused);               // test hook: 0 = the two kernels
-    if (fused && (c->farPass || c->farPass2 || c->searchDepth || c->priceParse || c->shortPass || MF_C(frameArg) != MF_F(frameArg))) fused = 0u;
+    const bool fused = !plan.farPass && !plan.farPass2 && !plan.searchDepth && !plan.priceParse && !plan.shortPass && MF_C(frameArg) == MF_F(frameArg);
     if (fused) {
         {
             const uint32_t tpb = GC_ZSTD_BLOCK_MAX >> g.tileLog;
             const uint32_t perV = ((gc_xcd_per(g.nTiles) + tpb - 1u) / tpb) * tpb;      // whole blocks per XCD class: a tile never waits for a tile of another class
             uint32_t* tw = c->mfTileWord + (size_t)frame0 * g.tilesPerFrame;
             HIPCHK(c, hipMemsetAsync(tw, 0, (size_t)g.nTiles * sizeof(uint32_t), st));
-            GC_LAUNCH(MFSEL(gc_mf_vparse_tile_kernel), perV * GC_XCDS, g.verifyT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perV, c->lazyDepth, (const uint32_t*)cnt,
+            GC_LAUNCH(MFSEL(gc_mf_vparse_tile_kernel), perV * GC_XCDS, g.verifyT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perV, plan.lazyDepth, (const uint32_t*)cnt,
                       (const GcMfEntry*)ent2, seqRaw, lit, meta, c->mfTicket + part * 16u + 8u, tw, prof);
         }
         for (int i = 10; i <= 12; i++) HIPCHK(c, hipEventRecord(ev[i], st));
@@ -465,7 +618,7 @@ static int launch_finder_part(gc_ctx* c, hipStream_t st, uint32_t part, const ui
     GC_LAUNCH(MFSEL(gc_mf_verify_kernel), perT * GC_XCDS, g.verifyT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt,
                    (const GcMfEntry*)ent2, rec);
     HIPCHK(c, hipEventRecord(ev[10], st));
-    if (c->farPass) {                                           // second pass with 16- / 12-byte keys, merged into rec (timed with W5)
+    if (plan.farPass) {                                         // second pass with 16- / 12-byte keys, merged into rec (timed with W5)
         GC_LAUNCH(MFSEL(gc_mf_count_far_kernel), perT * GC_XCDS, nParts, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, cnt);
         GC_LAUNCH(MFSEL(gc_mf_scan_kernel), g.nFrames, 1024, st, cnt, g.tilesPerFrame);
         GC_LAUNCH(MFSEL(gc_mf_scatter_far_kernel), perT * GC_XCDS, nParts, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt, ent);
@@ -473,7 +626,7 @@ static int launch_finder_part(gc_ctx* c, hipStream_t st, uint32_t part, const ui
         GC_LAUNCH(MFSEL(gc_mf_verify_far_kernel), perT * GC_XCDS, g.verifyT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt,
                   (const GcMfEntry*)ent2, rec);
     }
-    if (c->farPass2) {                                          // third pass of the far kind: keys of 32 / 24 bytes, capped records ranked by what lies behind the cap (gc_lz_window.hip MF_FAR2; timed with W5)
+    if (plan.farPass2) {                                        // third pass of the far kind: keys of 32 / 24 bytes, capped records ranked by what lies behind the cap (gc_lz_window.hip MF_FAR2; timed with W5)
         GC_LAUNCH(MFSEL(gc_mf_count_far2_kernel), perT * GC_XCDS, nParts, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, cnt);
         GC_LAUNCH(MFSEL(gc_mf_scan_kernel), g.nFrames, 1024, st, cnt, g.tilesPerFrame);
         GC_LAUNCH(MFSEL(gc_mf_scatter_far2_kernel), perT * GC_XCDS, nParts, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt, ent);
@@ -482,21 +635,21 @@ static int launch_finder_part(gc_ctx* c, hipStream_t st, uint32_t part, const ui
                   (const GcMfEntry*)ent2, rec);
     }
     HIPCHK(c, hipEventRecord(ev[11], st));
-    uint32_t* const chg = (c->searchDepth && c->shortPass && c->priceParse) ? c->mfChanged + (size_t)blk0 * (GC_ZSTD_BLOCK_MAX / 32u) : (uint32_t*)nullptr;      // which records W5b changes: what the pass with 4- / 3-byte keys looks at again (gc_lz_window.hip "continuation")
-    if (c->searchDepth) {                                       // W5b: follow match links (timed with W5)
+    uint32_t* const chg = (plan.searchDepth && plan.shortPass && plan.priceParse) ? c->mfChanged + (size_t)blk0 * (GC_ZSTD_BLOCK_MAX / 32u) : (uint32_t*)nullptr;      // which records W5b changes: what the pass with 4- / 3-byte keys looks at again (gc_lz_window.hip "continuation")
+    if (plan.searchDepth) {                                     // W5b: follow match links (timed with W5)
         uint32_t* rec2 = c->mfRec2 + (size_t)blk0 * GC_ZSTD_BLOCK_MAX;
-        GC_LAUNCH(MFSEL(gc_mf_deepen_kernel), perT * GC_XCDS, 256, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, c->searchDepth | (c->searchShallow << 8), (const uint32_t*)rec, rec2, chg);
+        GC_LAUNCH(MFSEL(gc_mf_deepen_kernel), perT * GC_XCDS, 256, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, plan.searchDepth | (plan.searchShallow << 8), (const uint32_t*)rec, rec2, chg);
         rec = rec2;
     }
     HIPCHK(c, hipEventRecord(ev[12], st));
-    const uint32_t litCtxArg = c->priceLitCtx | (blk0 != 0u ? 0x80000000u : 0u);   // bit 31: a later part -- the byte in front of src exists
+    const uint32_t litCtxArg = plan.priceLitCtx | (blk0 != 0u ? 0x80000000u : 0u);   // bit 31: a later part -- the byte in front of src exists
     const uint32_t* recDp = rec;                                // what W7 reads: the records, or the records + short candidates
-    if (c->priceParse && c->shortPass) {                        // third pass with 4- / 3-byte keys (timed with W5)
+    if (plan.priceParse && plan.shortPass) {                    // third pass with 4- / 3-byte keys (timed with W5)
         uint32_t* recN = rec == c->mfRec + (size_t)blk0 * GC_ZSTD_BLOCK_MAX ? c->mfRec2 + (size_t)blk0 * GC_ZSTD_BLOCK_MAX : c->mfRec + (size_t)blk0 * GC_ZSTD_BLOCK_MAX;
         // Overlapping frames list and link every position once per frame that holds it.  A match of 3-4 bytes MiBs back is never worth its distance, so this pass runs
         // over frames that tile the input (the plain geometry F: a frame then lies inside its group, whose start is as far back as the stages behind the finder let a match reach)
-        const uint32_t fbS = c->shortPlain ? MF_F(frameArg) : frameArg;                 // (the levels that are not after speed keep the overlap: the generator of lz-7zip copies 3-4 bytes from anywhere in its window, 32 MiB at FLZMA2 level 7: +0.26 % without)
-        const GcMfGeom gs = gc_mf_geom(n, fbS, c->mfFast != 0u);
+        const uint32_t fbS = plan.shortPlain ? MF_F(frameArg) : frameArg;               // (flzma2_plan: which levels keep the overlap)
+        const GcMfGeom gs = gc_mf_geom(n, fbS, plan.mfFast != 0u);
         const uint32_t perTs = gc_xcd_per(gs.nTiles), nListsS = gs.nFrames * nParts;
         uint32_t* cntS = c->mfCnt;
         GC_LAUNCH(MFSEL(gc_mf_count_short_kernel), perTs * GC_XCDS, nParts, st, src, (uint64_t)n, fbS, gs.nTiles, perTs, cntS);
@@ -505,21 +658,21 @@ static int launch_finder_part(gc_ctx* c, hipStream_t st, uint32_t part, const ui
         {   uint32_t* ticket_ = c->mfTicket + part * 16u + linkLaunch++;
             const uint32_t gridS = nListsS * GC_MF_LINK_SEGS < c->nCU * linkWpc ? nListsS * GC_MF_LINK_SEGS : c->nCU * linkWpc;
             GC_LAUNCH(MFSEL(gc_mf_link_kernel), gridS, 64, st, (const uint32_t*)cntS, (const GcMfEntry*)ent, ent2, gs.tilesPerFrame, gs.frameBytes, nListsS, ticket_); }
-        if (c->shortPlain) GC_LAUNCH(MFSEL(gc_mf_verify_short_kernel), perTs * GC_XCDS, gs.verifyT, st, src, (uint64_t)n, fbS, gs.nTiles, perTs, (const uint32_t*)cntS,
+        if (plan.shortPlain) GC_LAUNCH(MFSEL(gc_mf_verify_short_kernel), perTs * GC_XCDS, gs.verifyT, st, src, (uint64_t)n, fbS, gs.nTiles, perTs, (const uint32_t*)cntS,
                   (const GcMfEntry*)ent2, (const uint32_t*)rec, recN, (const uint32_t*)chg);
         else GC_LAUNCH(MFSEL(gc_mf_verify_shortb_kernel), perTs * GC_XCDS, gs.verifyT, st, src, (uint64_t)n, fbS, gs.nTiles, perTs, (const uint32_t*)cntS,
                   (const GcMfEntry*)ent2, (const uint32_t*)rec, recN, (const uint32_t*)chg);      // (with the catch-up: gc_lz_window.hip)
         recDp = recN;
     }
     HIPCHK(c, hipEventRecord(ev[5], st));
-    if (c->priceParse) {
+    if (plan.priceParse) {
         // greedy parse first (its symbol statistics become the block's price table), then the price-based parse W7 over the same
         // candidates + the short ones of W5s, written as records that W6 follows as they are (lazy 0)
         uint16_t* price = c->mfPrice + (size_t)blk0 * GC_PRICE_WORDS;
         uint16_t* rec3 = c->mfRec3 + (size_t)blk0 * GC_ZSTD_BLOCK_MAX;
         uint32_t* dp = c->mfDp + (size_t)blk0 * GC_ZSTD_BLOCK_MAX;
         uint32_t* wc = c->mfWinCost + (size_t)blk0 * 32u;
-        GC_LAUNCH(gc_mf_parse_kernel, perB * GC_XCDS, GC_MF_PARSE_T, st, src, (uint64_t)n, nBlocks, perB, c->lazyDepth, (const uint32_t*)rec, seqRaw, lit, meta, price, litCtxArg);
+        GC_LAUNCH(gc_mf_parse_kernel, perB * GC_XCDS, GC_MF_PARSE_T, st, src, (uint64_t)n, nBlocks, perB, plan.lazyDepth, (const uint32_t*)rec, seqRaw, lit, meta, price, litCtxArg);
         HIPCHK(c, hipEventRecord(ev[7], st));
         const uint32_t nChunkWg = (uint32_t)(((n + 2047u) / 2048u + 3u) / 4u), perC = gc_xcd_per(nChunkWg);
         if (shortBeside) HIPCHK(c, hipStreamWaitEvent(st, c->evShort[part], 0));
@@ -529,71 +682,58 @@ static int launch_finder_part(gc_ctx* c, hipStream_t st, uint32_t part, const ui
         // paths; B = every window under prices made from those counts (gc_lz_price.hip)
         uint32_t* dps = c->mfDpStat + (size_t)blk0 * GC_DPS_WORDS;
         HIPCHK(c, hipMemsetAsync(dps, 0, (size_t)nBlocks * GC_DPS_WORDS * sizeof(uint32_t), st));
-        uint32_t phase0 = 0; { uint32_t one = 0; if (gc_env_u32("GC_DP_PHASES", 1u, 2u, &one) && one == 1u) phase0 = 2u; }    // test hook: 1 = W6's prices only
-        // W7L (gc_lz_dpl.hip): one lane per window; LZMA with the four repeat distances at every node.  Test hook GC_DPL: 0 = W7 (a wave per window)
-        // 1: W7L everywhere (FLZMA2); 2: phase A in W7L, phase B per block in W7 or W7L by what phase A's paths did (gc_mf.h GC_DPS_RICH) -- zstd, where text repeats
-        // an offset in 1 % of its sequences and sources / binaries in 8-46 %: 125 MB of text at level 19 3.78 -> 4.75 GB/s (run r4s), the sizes of W7L where it matters.
-        // (FLZMA2 on the Silesia stand-in: half of the blocks sit right at the threshold, and a W7L launch takes as long for a few blocks as for all of them -- it ends with
-        // its slowest wave, and all of its waves fit the device at once -- so the two kernels' times add up: 40 -> 49 ms.)  Test hook GC_DPL: 0 = W7 with its own phase A
-        uint32_t laneDp = c->laneParse ? (c->lastCodecHint == 1 ? 1u : 2u) : 0u; gc_env_u32("GC_DPL", 0u, 2u, &laneDp);
-        if (c->lastCodecHint == 2 && !c->laneParse) laneDp = 0u;                        // (brotli, hook GC_BR_LANE=0: W7 only.  Qualities 8-11 run zstd's W7L kernels since round 6: the parse's last distances at every node, which B1 then codes as ring
-                                                                                        //  entries; 32 MiB at quality 9: shared objects 1.023 -> 0.980 x the reference, real sources 1.092 -> 1.038, text / web-text / lz-7zip as before -- phase B goes to W7 there)
         uint8_t* lpr = c->mfLitPrice + (size_t)blk0 * GC_ZSTD_BLOCK_MAX;
-        if (laneDp) GC_LAUNCH(gc_mf_litprice_kernel, perB * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perB, (const uint16_t*)price, litCtxArg, lpr);
+        if (plan.laneDp) GC_LAUNCH(gc_mf_litprice_kernel, perB * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perB, (const uint16_t*)price, litCtxArg, lpr);
         // (Round 5 built a re-priced SECOND pass over every window -- the first full pass counts its own paths, the second prices from those counts -- behind a hook: text -0.14 .. -0.25 %,
         //  real sources +1.6 %, FLZMA2 on shared objects -0.04 %, profiles/r05_zstd19.md.  Measured, not taken; removed in round 6.)
-        for (uint32_t pass = phase0 == 2u ? 1u : 0u; pass < 2u; pass++) {
-            const uint32_t phase = phase0 == 2u ? 2u : (pass == 0u ? 0u : 1u);
+        for (uint32_t pass = plan.dpPhases == 1u ? 1u : 0u; pass < 2u; pass++) {
+            const uint32_t phase = plan.dpPhases == 1u ? 2u : pass;      // (2: phase B under W6's prices)
             const uint32_t nDpWg = nBlocks * (phase == 0u ? 1u : 8u), perD = gc_xcd_per(nDpWg);
             uint32_t* wcp = phase == 0u ? (uint32_t*)nullptr : wc;
-            if (laneDp) {
-                // Windows of 2 KiB (one block per wave) where the 4 KiB ones leave the device half empty: W7L takes as long as ONE wave needs for its window, whatever the
-                // number of waves, as long as they are all resident (1 024 groups of 64 windows); a call of <= 1 024 blocks (128 MiB) has at most 512 groups of 4 KiB
-                // windows.  Round 4 measured 32 MiB 23.5 -> 13.6 ms and 128 MiB 25.4 -> 15.7 ms for +0.02 % (the Silesia stand-in) ... +0.36 % (shared objects) and left it
-                // off because the size bars sat at the band's edge; round 5 (merged model segments, overlapping frames) moved them: on at FLZMA2 levels 5-6.
-                uint32_t win2k = (c->smallWin2k && nBlocks <= 1024u) ? 1u : 0u; gc_env_u32("GC_DPL_WIN2K", 0u, 1u, &win2k);      // test hook
-                const bool w2 = win2k != 0u && phase != 0u;
+            if (plan.laneDp) {
+                // windows of 2 KiB (one block per wave) in phase B where the 4 KiB ones leave the device half empty (flzma2_plan)
+                const bool w2 = (plan.smallWin2k == 2u || (plan.smallWin2k == 1u && nBlocks <= 1024u)) && phase != 0u;
                 const uint32_t nItems = w2 ? nBlocks : (nBlocks + 1u) / 2u, perL = gc_xcd_per(nItems);     // a wave = two blocks (2 KiB windows: one)
-                const bool select = laneDp == 2u && phase == 1u && !w2;
-                const uint32_t phaseK = phase | (w2 ? 16u : 0u) | (select ? GC_DP_SELECT : 0u) | (c->allLengths ? GC_DP_ALLLEN : 0u);
+                const bool select = plan.laneDp == 2u && phase == 1u && !w2;
+                const uint32_t phaseK = phase | (w2 ? 16u : 0u) | (select ? GC_DP_SELECT : 0u) | (plan.allLengths ? GC_DP_ALLLEN : 0u);
                 if (select) {                                      // the blocks without repeats: W7
-                    if (c->priceMinLen <= 2u) GC_LAUNCH(gc_mf_dp2_kernel, perD * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perD, groupBlocks, phaseK, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp);
+                    if (plan.priceMinLen <= 2u) GC_LAUNCH(gc_mf_dp2_kernel, perD * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perD, groupBlocks, phaseK, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp);
                     else GC_LAUNCH(gc_mf_dp3_kernel, perD * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perD, groupBlocks, phaseK, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp);
                 }
-                if (c->priceMinLen <= 2u) {
-                    if (phase == 0u) GC_LAUNCH(gc_mf_dpl2s_kernel, perL * GC_XCDS, GC_DPL_THREADS, st, src, (uint64_t)n, nBlocks, perL, groupBlocks, phase | (c->allLengths ? GC_DP_ALLLEN : 0u), dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp, (const uint8_t*)lpr);
+                if (plan.priceMinLen <= 2u) {
+                    if (phase == 0u) GC_LAUNCH(gc_mf_dpl2s_kernel, perL * GC_XCDS, GC_DPL_THREADS, st, src, (uint64_t)n, nBlocks, perL, groupBlocks, phase | (plan.allLengths ? GC_DP_ALLLEN : 0u), dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp, (const uint8_t*)lpr);
                     else GC_LAUNCH(gc_mf_dpl2_kernel, perL * GC_XCDS, GC_DPL_THREADS, st, src, (uint64_t)n, nBlocks, perL, groupBlocks, phaseK, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp, (const uint8_t*)lpr);
                 } else {                                           // zstd, and brotli with the ring's first entries standing in for zstd's repeat offsets
-                    if (phase == 0u) GC_LAUNCH(gc_mf_dplzs_kernel, perL * GC_XCDS, GC_DPL_THREADS, st, src, (uint64_t)n, nBlocks, perL, groupBlocks, phase | (c->allLengths ? GC_DP_ALLLEN : 0u), dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp, (const uint8_t*)lpr);
+                    if (phase == 0u) GC_LAUNCH(gc_mf_dplzs_kernel, perL * GC_XCDS, GC_DPL_THREADS, st, src, (uint64_t)n, nBlocks, perL, groupBlocks, phase | (plan.allLengths ? GC_DP_ALLLEN : 0u), dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp, (const uint8_t*)lpr);
                     else GC_LAUNCH(gc_mf_dplz_kernel, perL * GC_XCDS, GC_DPL_THREADS, st, src, (uint64_t)n, nBlocks, perL, groupBlocks, phaseK, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp, (const uint8_t*)lpr);
                 }
             } else
-            if (c->priceMinLen <= 2u) GC_LAUNCH(gc_mf_dp2_kernel, perD * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perD, groupBlocks, phase, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp);
+            if (plan.priceMinLen <= 2u) GC_LAUNCH(gc_mf_dp2_kernel, perD * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perD, groupBlocks, phase, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp);
             else GC_LAUNCH(gc_mf_dp3_kernel, perD * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perD, groupBlocks, phase, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp);
         }
         HIPCHK(c, hipEventRecord(ev[9], st));
         GC_LAUNCH(gc_mf_parse_kernel, perB * GC_XCDS, GC_MF_PARSE_T, st, src, (uint64_t)n, nBlocks, perB, 0u, (const uint32_t*)dp, seqRaw, lit, meta, (uint16_t*)nullptr, 0u);
-    } else if (c->ringParse) {
-        if ((c->ringParse >> 8) & 0xFFu)                               // W6r on the blocks that W6's parse shows to come back to their last distances
-            GC_LAUNCH(gc_mf_parse_kernel, perB * GC_XCDS, GC_MF_PARSE_T, st, src, (uint64_t)n, nBlocks, perB, c->lazyDepth, (const uint32_t*)rec, seqRaw, lit, meta, (uint16_t*)nullptr, 0u);
-        GC_LAUNCH(gc_mf_ringparse_kernel, perB * GC_XCDS, c->ringGeom, st, src, (uint64_t)n, nBlocks, perB, c->lazyDepth < 1u ? c->lazyDepth : 1u, c->ringParse, (const uint32_t*)rec, seqRaw, lit, meta);
+    } else if (plan.ringParse) {
+        if ((plan.ringParse >> 8) & 0xFFu)                               // W6r on the blocks that W6's parse shows to come back to their last distances
+            GC_LAUNCH(gc_mf_parse_kernel, perB * GC_XCDS, GC_MF_PARSE_T, st, src, (uint64_t)n, nBlocks, perB, plan.lazyDepth, (const uint32_t*)rec, seqRaw, lit, meta, (uint16_t*)nullptr, 0u);
+        GC_LAUNCH(gc_mf_ringparse_kernel, perB * GC_XCDS, plan.ringGeom, st, src, (uint64_t)n, nBlocks, perB, plan.lazyDepth < 1u ? plan.lazyDepth : 1u, plan.ringParse, (const uint32_t*)rec, seqRaw, lit, meta);
     }
     else
-        GC_LAUNCH(gc_mf_parse_kernel, perB * GC_XCDS, GC_MF_PARSE_T, st, src, (uint64_t)n, nBlocks, perB, c->lazyDepth, (const uint32_t*)rec, seqRaw, lit, meta, (uint16_t*)nullptr, 0u);
+        GC_LAUNCH(gc_mf_parse_kernel, perB * GC_XCDS, GC_MF_PARSE_T, st, src, (uint64_t)n, nBlocks, perB, plan.lazyDepth, (const uint32_t*)rec, seqRaw, lit, meta, (uint16_t*)nullptr, 0u);
     HIPCHK(c, hipEventRecord(ev[6], st));
     (void)prof;
     return GC_OK;
 }
 
 // whole input as one part on the main stream
-static int launch_finder(gc_ctx* c, const uint8_t* src, size_t n, uint32_t frameBlocks, unsigned long long* prof)
+static int launch_finder(gc_ctx* c, const GcLzPlan& plan, const uint8_t* src, size_t n, uint32_t frameBlocks, unsigned long long* prof)
 {
     c->mfTimed = false;
-    int rc = ensure_finder_workspace(c, n, frameBlocks);
+    int rc = ensure_finder_workspace(c, plan, n, frameBlocks);
     if (rc != GC_OK) return rc;
-    rc = launch_finder_part(c, c->stream, 0, src, n, frameBlocks, 0, prof);
+    rc = launch_finder_part(c, plan, c->stream, 0, src, n, frameBlocks, 0, prof);
     if (rc != GC_OK) return rc;
-    c->mfTimed = MF_F(frameBlocks) > 1u; c->mfParts = 1; c->mfPriced = c->mfTimed && c->priceParse != 0u;
+    c->mfTimed = MF_F(frameBlocks) > 1u; c->mfParts = 1; c->mfPriced = c->mfTimed && plan.priceParse != 0u;
     return GC_OK;
 }
 
@@ -632,22 +772,6 @@ extern "C" int gc_mf_pass_timing(gc_ctx* c, float ms[4])
     return GC_OK;
 }
 
-// zstd level -> blocks per frame.  Levels 1-2 (the reference's `fast` strategy, clevels.h:29-30) use the block-local finder and
-// one frame per block; level 3 and up (dfast and stronger, clevels.h:31-47, windowLog >= 21) use the windowed finder with
-// 8 MiB frames.
-// Every level runs the windowed finder over 8 MiB frames (round 3).  Levels 1-2 used the block-local finder before -- a 128 KiB window against the
-// 512 KiB / 1 MiB windows of the reference's levels 1 / 2 (clevels.h:26-27): 1.026 x its level 1 on text, 1.085 x its level 2 (run r03_levels).
-// The block-local kernel K1 still serves inputs of one block.
-static uint32_t zstd_frame_blocks(int level) { return level >= 18 ? GC_MF_WIDE_MAX_FRAME_BLOCKS : GC_MF_MAX_FRAME_BLOCKS; }       // (round 6: 16 MiB windows at 18-22 -- the reference: windowLog 23 at 18-19, 25-27 at 20-22, clevels.h:46-50)
-// Levels 16-22: the finder's frames overlap (gc_mf.h "Overlapping frames") inside groups that are the zstd frames.  The reference: windowLog 22 at level 16-17, 23 at 18-19,
-// 25 / 26 / 27 at 20 / 21 / 22 (clevels.h:44-50), one frame, ZSTDMT jobs of four windows overlapping by one (zstdmt_compress.c:741-747).  Here the window stays 8 MiB
-// (23-bit positions); what the levels choose is how much of it a position is sure to have behind it: stride 4 MiB = 4-8 MiB of history at 16-19, stride 2 MiB = 6-8 MiB at
-// 20-22 (each halving of the stride lists and links every position once more: W1..W4 of the three passes).
-static uint32_t zstd_group_blocks(int level) { return level >= 16 ? 4u * GC_MF_MAX_FRAME_BLOCKS : GC_MF_MAX_FRAME_BLOCKS; }     // 32 MiB zstd frames (= shard grain) / 8 MiB
-static uint32_t zstd_stride_blocks(int level) { return (level == 18 || level == 19) ? GC_MF_MAX_FRAME_BLOCKS : GC_MF_MAX_FRAME_BLOCKS / 2u; }      // a position is sure of 4 MiB of history at 16-17 (8 MiB windows every 4 MiB), of 8 MiB -- the reference's whole window -- at 18-19 (16 MiB windows every 8 MiB), of 12 MiB at 20-22 (every 4 MiB; round 5: 8 MiB windows every 2 MiB)
-// zstd level -> match links followed per position (the reference's searchLog grows the same way: clevels.h:25-47)
-static uint32_t zstd_search_depth(int level) { return level < 6 ? 0u : (level < 10 ? 2u : (level < 16 ? 4u : (level < 18 ? 8u : 16u))); }
-
 extern "C" int gc_zstd_compress_device(gc_ctx* c, const void* d_src, size_t n, void* d_dst, size_t dstCap, int level)
 {
     if (!c || (!d_src && n) || !d_dst) return GC_ERR_PARAM;
@@ -668,64 +792,23 @@ extern "C" int gc_zstd_compress_device(gc_ctx* c, const void* d_src, size_t n, v
     if (rc != GC_OK) return rc;
     const uint8_t* src = (const uint8_t*)d_src;
     if (c->profOn) { HIPCHK(c, hipMemsetAsync(c->prof, 0, (GC_LZ_PHASES + GC_SEQ_PHASES) * sizeof(unsigned long long), c->stream)); c->profBlocks = nBlocks; }
-    uint32_t frameBlocks = zstd_frame_blocks(level);
-    if (frameBlocks > 1u && c->dbgFrameBlocks) frameBlocks = c->dbgFrameBlocks;                              // test hook: small frames
-    if (frameBlocks > nBlocks) frameBlocks = nBlocks;                                                       // short input: one frame
-    c->lazyDepth = level >= 6 ? 2u : 1u;          // the reference's lazy2 begins at level 8 of its table; deeper look-ahead from 6 here
-    c->mfFast = level <= 6 ? 1u : 0u;             // no far pass below level 7: the fast geometry (gc_mf.h)
-    gc_env_u32("GC_MF_FAST", 0u, 1u, &c->mfFast);                                              // test hook
-    // (Listing half of the positions, chosen by content, was measured at level 3 in rounds 2 and 5 -- 1 GB of text 43.2 -> 39.0 ms for +3.5-4.5 % size, real sources 0.949 -> 1.158 x
-    //  the reference -- and again in round 6's lab with the catch-up in place (tools/zstd_parse_lab.c policy 4: shared objects +10 %): not taken, its kernels are gone.)
-    c->searchDepth = zstd_search_depth(level); c->searchShallow = c->searchDepth < 2u ? c->searchDepth : 2u;
-    if (gc_env_u32("GC_SEARCH_DEPTH", 0u, 64u, &c->searchDepth)) c->searchShallow = c->searchDepth < 2u ? c->searchDepth : 2u;      // test hook
-    gc_env_u32("GC_SEARCH_SHALLOW", 0u, 64u, &c->searchShallow);                                // test hook: links followed by every position
-    c->ringParse = 0u;
-    c->farPass = level >= 5 ? 1u : 0u;            // where the reference searches chains / trees (lazy2 and up).  Measured (run 29, 32 MiB): level 9
-                                                  // 1.027 -> 0.984 x the reference on text, level 12 1.040 -> 1.001 x.  Round 6: from level 5 (was 7) -- the reference's greedy / lazy
-                                                  // strategies at 5-6 walk hash chains (zstd_lazy.c:667, searchLog 3: clevels.h:33-34), and on real sources the first pass alone was
-                                                  // 1.135 x its level 5 and 1.136 x its level 6 (32 / 8 MiB, run s4: nobody had looked); with the two far passes 0.932 / 0.984 (emulator, 8 MiB)
-    c->shortPass = level >= 5 ? 1u : 0u;          // the reference's btopt strategies search 3-byte matches (minMatch 3, clevels.h:44-47); from level 10 since round 3, from level 7 since round 6, see priceParse
-    gc_env_u32("GC_FAR_PASS", 0u, 1u, &c->farPass); gc_env_u32("GC_SHORT_PASS", 0u, 1u, &c->shortPass);   // test hooks
-    c->shortPlain = 0u; c->smallWin2k = 0u;
-    c->allLengths = level >= 18 ? 1u : 0u;        // levels 16-17 (the reference: btopt / btultra with searchLog 5) keep the sparse lengths and the two far passes; 18-22 (btultra / btultra2, searchLog 6-9) price every length
-    c->farPass2 = (level >= 5 && level != 16 && level != 17) ? 1u : 0u; gc_env_u32("GC_FAR2_PASS", 0u, 1u, &c->farPass2);      // keys of 32 / 24 bytes where the reference searches chains / trees for the LONGEST match: real sources, emulator, 8 MiB:
-                                                                                              // level 9 1.118 -> 1.050 x the reference, level 19 1.115 -> 1.097
-    c->laneParse = level >= 16 ? 1u : 0u;         // the reference's btopt .. btultra2 (clevels.h:44-50) price its three repeat offsets at every position; real sources / binaries at level 19
-                                                  // (emulator, 4 MiB): 1.109 / 1.124 x the reference with W7, 1.081 / 1.075 with W7L.  Levels 10-15 (the reference: lazy2 / btlazy2) keep W7
-    c->lastCodecHint = 0; c->priceMinLen = 3u; c->priceLitCtx = 0u;     // zstd: matches of >= 3 bytes, literals without context (one Huffman table per block)
-    c->priceParse = level >= 5 ? 1u : 0u;         // the reference's btopt / btultra strategies start at level 16 (clevels.h:44-47), its levels 10-15 are lazy2 / btlazy2 over deep
-                                                  // chains and trees; the greedy / lazy2 parse over this finder's 3-6 candidates was 1.03 x them on lz-7zip (levels 10 and 12, run r03_z12),
-                                                  // the price-based parse 0.98 -- so it started at level 10 in round 3.  Round 6: from level 7, where the far passes start.  The reference's
-                                                  // lazy2 at 7-9 picks the longest of 16-32 tagged row candidates (zstd_lazy.c:1141); the lazy parse over this finder's gain-merged record was
-                                                  // 1.058-1.062 x it on real shared objects (level 7 LARGER than level 5: a far match that wins by `4 len - log2 offset` is often dearer than the
-                                                  // near one it replaces); with the short pass + the price-based parse 1.026 / 1.028 (emulator, 8 MiB; real sources 1.038 -> 0.978, text 0.942 -> 0.909).
-                                                  // And from level 5 once the far passes start there: levels 5 / 6 on shared objects 1.043 / 1.048 with the lazy parse over the merged records, 1.014 / 1.017 with
-                                                  // this one (real sources 0.891).  Levels 5-12 now differ in the geometry (5-6: the fast one), the links followed (0 / 2 / 4) and nothing else
-    gc_env_u32("GC_PRICE_PARSE", 0u, 1u, &c->priceParse);                                      // test hook
-    // Overlapping finder frames (gc_mf.h) from level 16: the zstd frame becomes the GROUP (the reference's own frames are the whole input with a sliding window).
-    uint32_t zGroup = zstd_group_blocks(level); const bool grpHook = gc_env_u32("GC_MF_GROUP", 1u, 65535u, &zGroup);      // test hook: blocks per group (with GC_FRAME_BLOCKS and GC_MF_STRIDE: overlapping frames of a few blocks)
-    uint32_t zArg = frameBlocks;                                                               // what the finder takes
-    if (zGroup > frameBlocks && (frameBlocks == zstd_frame_blocks(level) || grpHook) && nBlocks > frameBlocks) {
-        uint32_t stride = zstd_stride_blocks(level); gc_env_u32("GC_MF_STRIDE", 1u, GC_MF_MAX_FRAME_BLOCKS, &stride);      // test hook (blocks; 64 = no overlap)
-        if (stride < frameBlocks && (frameBlocks % stride) == 0u && ((zGroup - frameBlocks) % stride) == 0u) zArg = GC_MF_GEOM_ARG(frameBlocks, stride, zGroup);
-    }
+    const GcLzPlan plan = with_hooks(zstd_plan(level));
+    const uint32_t zArg = lz_frame_arg(GC_CODEC_ZSTD, level, nBlocks, c->dbgFrameBlocks);      // what the finder takes: overlapping frames from level 16, whose groups are the zstd frames
     const uint32_t zFrameBlocks = MF_C(zArg);                                                  // blocks per zstd frame
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
     // The input can be taken in frame-aligned PARTS, the finder of part p + 1 (main stream) beside the entropy stage of part p (sequences on
     // stream2, literals on stream3).  Measured on MI355X (run r3_g, 1 GB of text at level 3): 1 part 30.9 ms, 2 parts 32.2, 4 parts 32.0,
     // 8 parts 35.2; 100 MB: 3.9 / 5.0 / 7.1 ms -- kernels that run beside each other take the CUs' LDS and wave slots from one another and
-    // every part pays its own launch tails.  One part it is; the hook keeps the path exercised.
+    // every part pays its own launch tails.  One part it is, unless the entry lists need more (mf_auto_parts) or test hook GC_PART_FRAMES asks for parts of that many frames.
     const uint32_t nFrames = (nBlocks + zFrameBlocks - 1u) / zFrameBlocks;                      // (zstd frames = the finder's groups)
-    uint32_t nParts = 1u;
-    gc_env_u32("GC_ZSTD_PARTS", 1u, GC_MAX_PARTS, &nParts);                                    // test hook
-    if (c->dbgPartFrames) nParts = nFrames / c->dbgPartFrames;
+    uint32_t nParts = c->dbgPartFrames ? nFrames / c->dbgPartFrames : 1u;
     { const uint32_t autoParts = mf_auto_parts(n, zArg); if (nParts < autoParts) nParts = autoParts; }      // (entry lists beyond the budget: ensure_finder_workspace)
     if (nParts > nFrames) nParts = nFrames;
     if (nParts > GC_MAX_PARTS) nParts = GC_MAX_PARTS;
     if (nParts < 1u) nParts = 1u;
     c->mfTimed = false;
     const uint32_t framesPerPart = (nFrames + nParts - 1u) / nParts;
-    rc = ensure_finder_workspace(c, n, zArg, (size_t)framesPerPart * zFrameBlocks * GC_ZSTD_BLOCK_MAX);
+    rc = ensure_finder_workspace(c, plan, n, zArg, (size_t)framesPerPart * zFrameBlocks * GC_ZSTD_BLOCK_MAX);
     if (rc != GC_OK) return rc;
     uint32_t usedParts = 0;
     for (uint32_t p = 0; p < nParts; p++) {
@@ -734,7 +817,7 @@ extern "C" int gc_zstd_compress_device(gc_ctx* c, const void* d_src, size_t n, v
         const size_t off = (size_t)blk0 * GC_ZSTD_BLOCK_MAX;
         const size_t len = (size_t)framesPerPart * zFrameBlocks * GC_ZSTD_BLOCK_MAX < n - off ? (size_t)framesPerPart * zFrameBlocks * GC_ZSTD_BLOCK_MAX : n - off;
         const uint32_t pBlocks = gc_num_blocks(len);
-        rc = launch_finder_part(c, c->stream, p, src + off, len, zArg, blk0, c->profOn ? c->prof : nullptr);
+        rc = launch_finder_part(c, plan, c->stream, p, src + off, len, zArg, blk0, c->profOn ? c->prof : nullptr);
         if (rc != GC_OK) return rc;
         HIPCHK(c, hipEventRecord(c->evPart[p][0], c->stream));                                 // finder of this part done
         if (p + 1u == nParts || blk0 + pBlocks >= nBlocks) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
@@ -758,7 +841,7 @@ extern "C" int gc_zstd_compress_device(gc_ctx* c, const void* d_src, size_t n, v
                   c->litSec + (size_t)blk0 * GC_LITSEC_STRIDE, c->info + blk0);
         usedParts = p + 1u;
     }
-    c->mfTimed = frameBlocks > 1u; c->mfParts = usedParts; c->mfPriced = c->mfTimed && c->priceParse != 0u;
+    c->mfTimed = MF_F(zArg) > 1u; c->mfParts = usedParts; c->mfPriced = c->mfTimed && plan.priceParse != 0u;
     HIPCHK(c, hipEventRecord(c->ev[4], c->stream2));
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream3));
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev[2], 0));
@@ -848,7 +931,6 @@ extern "C" int gc_zstd_phase_profile(gc_ctx* c, double cyclesPerBlock[GC_LZ_PHAS
 // level -> model segment size (gc_lzma2.h): smaller segments = more model waves in flight (faster), more state resets (larger).
 static uint32_t flzma2_seg_log(int level)
 {
-    { uint32_t v = 0; if (gc_env_u32("GC_SEG_LOG", GC_LZMA_SEG_LOG_MIN, GC_LZMA_SEG_LOG_MAX, &v)) return v; }   // test hook
     if (level <= 1) return 14u;
     if (level == 2) return 17u;     // (run r03_fl2ab, silesia-like 32 MiB: 16 KiB segments 1.032 x the reference's level 2, 32 KiB 1.022, 128 KiB 1.012)
     if (level <= 4) return 15u;
@@ -861,15 +943,6 @@ extern "C" size_t gc_flzma2_compress_bound(size_t n)
     const size_t nChunks = (n + GC_LZMA_RC_SIZE - 1) >> GC_LZMA_RC_LOG;
     return n + nChunks * 6u + 16u;
 }
-
-// level -> blocks per match-finder frame.  Every level runs the windowed finder over 8 MiB frames (round 3; levels 1-2 used the block-local
-// finder before: a 128 KiB window against the reference's 1-2 MiB dictionaries, fl2_compress.c:52-63, was 12-24 % behind it, run r03_levels).
-static uint32_t flzma2_frame_blocks(int level) { return level >= 7 ? GC_MF_WIDE_MAX_FRAME_BLOCKS : GC_MF_MAX_FRAME_BLOCKS; }     // (round 6: 16 MiB windows at 7-9 -- the reference: dictionaries of 32 / 64 / 64 MiB, fl2_compress.c:74-86)
-// Levels 7-9 (the reference: dictionaries of 64 / 64 / 128 MiB, fl2_compress.c:59-62): overlapping finder frames (gc_mf.h) in groups of 64 MiB, stride 4 MiB at 7, 2 MiB at 8-9
-// (a position is sure of 4 / 6 MiB of history; the window itself stays 8 MiB: 23-bit positions).  Levels 1-6: frames that tile the input.
-// Levels 5-6 (round 5; the reference: 16 / 32 MiB dictionaries): groups of 16 MiB, stride 4 MiB -- real shared objects, 32 MiB at level 5 on the emulator: 1.0186 -> 1.0148 x the reference
-static uint32_t flzma2_group_blocks(int level) { return level >= 7 ? 8u * GC_MF_MAX_FRAME_BLOCKS : (level >= 5 ? 2u * GC_MF_MAX_FRAME_BLOCKS : GC_MF_MAX_FRAME_BLOCKS); }
-static uint32_t flzma2_stride_blocks(int level) { return level >= 8 ? GC_MF_MAX_FRAME_BLOCKS / 2u : (level >= 7 ? GC_MF_MAX_FRAME_BLOCKS : GC_MF_MAX_FRAME_BLOCKS / 2u); }      // 5-6: 4 MiB (8 MiB windows); 7: 8 MiB, 8-9: 4 MiB (16 MiB windows: 8-16 / 12-16 MiB of history)
 
 // dictionary-size property byte of the 7z coder (Lzma2Encoder.cpp:353-364): dict = (2|(p&1)) << (p/2+11).
 // Matches never reach back further than the start of their frame: 128 KiB (p = 10) or 8 MiB (p = 22).
@@ -907,33 +980,8 @@ extern "C" int gc_flzma2_compress_device(gc_ctx* c, const void* d_src, size_t n,
             if ((rc = mf_grow(c, (void**)&c->lzRcOut, &c->lzRcOutCap, needRc, "range-coder staging")) != GC_OK) return rc;
         }
     }
-    uint32_t frameBlocks = flzma2_frame_blocks(level);
-    c->lazyDepth = level >= 5 ? 2u : 1u;
-    c->mfFast = 0;
-    c->searchShallow = level >= 5 ? 2u : 0u;
-    c->searchDepth = level >= 5 ? (level >= 8 ? 16u : 12u) : 0u;    // links followed where a tile has long matches, by the positions that start one (two links elsewhere: gc_mf_deepen_kernel).
-                                                                    // Real source text (64 MiB): two links everywhere 1.030 x the reference, six everywhere 1.017 (run r03_depth)
-    c->ringParse = 0u;
-    c->farPass = level >= 3 ? 1u : 0u;            // the reference's match table resolves to depth 42 at level 5 (fl2_compress.c:37-104);
-                                                  // level 3 (run 30x, 32 MiB): 1.071 -> 1.026 x the reference on text
-    c->shortPass = level >= 3 ? 1u : 0u;          // ... and holds the nearest match of >= 2 bytes for every position
-    gc_env_u32("GC_FAR_PASS", 0u, 1u, &c->farPass); gc_env_u32("GC_SHORT_PASS", 0u, 1u, &c->shortPass);   // test hooks
-    if (gc_env_u32("GC_SEARCH_DEPTH", 0u, 64u, &c->searchDepth)) c->searchShallow = c->searchDepth < 2u ? c->searchDepth : 2u;
-    c->shortPlain = level < 7 ? 1u : 0u; c->allLengths = 0u;
-    c->smallWin2k = (level == 5 || level == 6) ? 1u : 0u;
-    c->farPass2 = level >= 7 ? 1u : 0u; gc_env_u32("GC_FAR2_PASS", 0u, 1u, &c->farPass2);      // keys of 32 / 24 bytes (gc_lz_window.hip MF_FAR2) at the ultra levels
-    c->laneParse = 1u; c->lastCodecHint = 1; c->priceMinLen = 2u; c->priceLitCtx = 7u;
-    c->priceParse = level >= 3 ? 1u : 0u;         // the reference's FL2_opt strategy starts at level 3 of its 7-Zip table (fl2_compress.c:52-63); round 3 (run r03_fl2ab): level 3 with
-                                                  // the greedy parse was 1.038 x the reference on silesia-like, with the price-based parse 1.002
-    gc_env_u32("GC_PRICE_PARSE", 0u, 1u, &c->priceParse);                                      // test hook: 0 = greedy parse only
-    if (frameBlocks > 1u && c->dbgFrameBlocks) frameBlocks = c->dbgFrameBlocks;
-    if (frameBlocks > nBlocks) frameBlocks = nBlocks;
-    uint32_t fArg = frameBlocks;                                                               // what the finder takes: overlapping frames from level 7 (gc_mf.h)
-    { uint32_t grp = flzma2_group_blocks(level); const bool grpHook = gc_env_u32("GC_MF_GROUP", 1u, 65535u, &grp);      // test hook: blocks per group (with GC_FRAME_BLOCKS and GC_MF_STRIDE: overlapping frames of a few blocks)
-      if (grp > frameBlocks && (frameBlocks == flzma2_frame_blocks(level) || grpHook) && nBlocks > frameBlocks) {
-          uint32_t stride = flzma2_stride_blocks(level); gc_env_u32("GC_MF_STRIDE", 1u, GC_MF_MAX_FRAME_BLOCKS, &stride);      // test hook (blocks; 64 = no overlap)
-          if (stride < frameBlocks && (frameBlocks % stride) == 0u && ((grp - frameBlocks) % stride) == 0u) fArg = GC_MF_GEOM_ARG(frameBlocks, stride, grp);
-      } }
+    const GcLzPlan plan = with_hooks(flzma2_plan(level));
+    const uint32_t fArg = lz_frame_arg(GC_CODEC_FLZMA2, level, nBlocks, c->dbgFrameBlocks);    // what the finder takes: overlapping frames from level 5
     const uint32_t groupBlocks = MF_C(fArg);
     // parts: ONE by default.  Overlapping the stages of several parts was measured and lost (212 MB: 33.9 ms with 4 parts against
     // 24.3 ms with one, profiles/r01_run8_flzma2_kernel_stats.md): model and range coder are chains whose duration is set by the
@@ -944,22 +992,20 @@ extern "C" int gc_flzma2_compress_device(gc_ctx* c, const void* d_src, size_t n,
     { const uint32_t autoParts = mf_auto_parts(n, fArg); if (nParts < autoParts) nParts = autoParts; }      // (entry lists beyond the budget: ensure_finder_workspace)
     if (nParts > GC_MAX_PARTS) nParts = GC_MAX_PARTS;
     if (nParts > nFrames) nParts = nFrames;
-    if (frameBlocks <= 1u) nParts = 1u;
+    if (MF_F(fArg) <= 1u) nParts = 1u;
     {   // the largest part (parts are whole groups: the split below)
         uint32_t maxGroups = 0, g0 = 0;
         for (uint32_t p = 0; p < nParts; p++) { const uint32_t g1 = (uint32_t)(((uint64_t)nFrames * (p + 1u)) / nParts); if (g1 - g0 > maxGroups) maxGroups = g1 - g0; g0 = g1; }
-        rc = ensure_finder_workspace(c, n, fArg, (size_t)maxGroups * groupBlocks * GC_ZSTD_BLOCK_MAX);
+        rc = ensure_finder_workspace(c, plan, n, fArg, (size_t)maxGroups * groupBlocks * GC_ZSTD_BLOCK_MAX);
         if (rc != GC_OK) return rc;
     }
     c->mfTimed = false; c->nParts = nParts;
     const uint32_t segPerBlock = GC_ZSTD_BLOCK_MAX >> segLog;
-    uint32_t mergeWords = level <= 6 ? 32768u : GC_LZMA_RC_MERGE_WORDS;                        // coded bits of one LZMA2 chunk = the chain of ONE lane of L3.  Levels <= 6 (run s9, 211.9 MB): 49 152 -> 32 768 words takes 1.65 ms off L3
+    const uint32_t mergeWords = level <= 6 ? 32768u : GC_LZMA_RC_MERGE_WORDS;                  // coded bits of one LZMA2 chunk = the chain of ONE lane of L3.  Levels <= 6 (run s9, 211.9 MB): 49 152 -> 32 768 words takes 1.65 ms off L3
                                                                                                // (5.98 -> 4.33) for +0.06 % size (10 bytes of header and coder flush per chunk)
-    gc_env_u32("GC_RC_MERGE_WORDS", 0u, GC_LZMA_RC_MERGE_WORDS, &mergeWords);                  // test hook: 0 = one LZMA2 chunk per rc chunk
     uint32_t rep4 = 1;                                                                         // rep2 / rep3 coding in L2 (gc_lzma2_enc.hip LzLru); test hook: 0 = rep0 / rep1 only
     gc_env_u32("GC_L2_REP4", 0u, 1u, &rep4);
-    uint32_t litSel = 1;                                                                       // lc / lp per model segment (gc_lzma2_model_kernel); test hook: 0 = the reference's lc 3 / lp 0 everywhere
-    gc_env_u32("GC_L2_LITSEL", 0u, 1u, &litSel);
+    const uint32_t litSel = 1;                                                                 // lc / lp per model segment (gc_lzma2_model_kernel); 0 = the reference's lc 3 / lp 0 everywhere
     uint32_t wordCap = GC_LZMA_STREAM_WORDS(segLog);                                           // words a segment may produce before it is stored instead
     gc_env_u32("GC_SEG_WORD_CAP", 1u, GC_LZMA_STREAM_WORDS(segLog), &wordCap);                  // test hook: a low cap sends ordinary segments down that path
     // model segments over 2 / 4 / 8 blocks where the parse prices them within what one block of poorly compressible data costs (gc_lzma2_model_kernel): level >= 5.
@@ -968,10 +1014,9 @@ extern "C" int gc_flzma2_compress_device(gc_ctx* c, const void* d_src, size_t n,
     gc_env_u32("GC_SEG_MERGE", 0u, 8u, &segMerge);                                              // test hook: 0 = every block a segment of its own (round 4)
     if (segMerge & (segMerge - 1u)) segMerge = 4u;
     while (segMerge > 1u && nBlocks > groupBlocks && (groupBlocks % segMerge) != 0u) segMerge >>= 1;      // (groups are aligned to the input: they must not straddle frames, or a frame-aligned shard would differ from the whole input's bytes)
-    uint32_t mergeBudget = 16u * 655360u;                                                      // 640 Ki coded bits (1/16 bit units) = 5 bits per byte of ONE 128 KiB block.  Measured on 211.9 MB (run s9, model kernel / size):
+    const uint32_t mergeBudget = 16u * 655360u;                                                // 640 Ki coded bits (1/16 bit units) = 5 bits per byte of ONE 128 KiB block.  Measured on 211.9 MB (run s9, model kernel / size):
                                                                                                // 896 Ki -- the longest chain the launch has anyway, PCM-like data -- 17.0 ms on the Silesia stand-in and 21.5 ms on shared objects
                                                                                                // (the estimate is the PARSE's: the model's chain comes out longer); 640 Ki 14.4 / 14.5 ms, as without merging, for +0.01 / +0.05 % size
-    { uint32_t kbits = 0; if (gc_env_u32("GC_SEG_MERGE_KBITS", 1u, 4096u, &kbits)) mergeBudget = kbits * 16384u; }
     uint8_t* const segKind = c->lzProps + (size_t)c->capBlocks * (GC_ZSTD_BLOCK_MAX >> GC_LZMA_SEG_LOG_MIN);
     if (c->profOn) { HIPCHK(c, hipMemsetAsync(c->prof, 0, (GC_LZ_PHASES + GC_SEQ_PHASES) * sizeof(unsigned long long), c->stream)); c->profBlocks = 1u; }   // L2 phase sums (raw)
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
@@ -985,7 +1030,7 @@ extern "C" int gc_flzma2_compress_device(gc_ctx* c, const void* d_src, size_t n,
         hipEvent_t* ev = c->evPart[p];
         // stage 1 (main stream): match finder + item lists
         HIPCHK(c, hipEventRecord(ev[0], c->stream));
-        rc = launch_finder_part(c, c->stream, p, src + off, pn, fArg, blk0, nullptr);
+        rc = launch_finder_part(c, plan, c->stream, p, src + off, pn, fArg, blk0, nullptr);
         if (rc != GC_OK) return rc;
         HIPCHK(c, hipEventRecord(ev[1], c->stream));
         GC_LAUNCH(gc_lzma2_prep_kernel, pBlocks, 256, c->stream, (const GcSeqRaw*)(c->seqRaw + (size_t)blk0 * GC_MAX_SEQ_PER_BLOCK),
@@ -997,7 +1042,7 @@ extern "C" int gc_flzma2_compress_device(gc_ctx* c, const void* d_src, size_t n,
         GC_LAUNCH(gc_lzma2_model_kernel, pSegs, 64, c->stream2, src + off, (uint64_t)pn, (const uint64_t*)(c->lzM + (size_t)blk0 * GC_LZMA_MAX_ITEMS),
                   (const uint32_t*)(c->lzNM + blk0), segLog, (uint32_t)(off != 0u ? 1u : 0u),
                   c->lzStream + (size_t)blk0 * segPerBlock * GC_LZMA_STREAM_WORDS(segLog), c->lzInfo + (size_t)blk0 * GC_LZMA_RC_PER_BLOCK,
-                  (const uint32_t*)((c->priceParse && frameBlocks > 1u) ? c->mfWinCost + (size_t)blk0 * 32u : nullptr),
+                  (const uint32_t*)((plan.priceParse && MF_F(fArg) > 1u) ? c->mfWinCost + (size_t)blk0 * 32u : nullptr),
                   c->profOn ? c->prof : nullptr, mergeWords, wordCap, rep4, c->lzProps + (size_t)blk0 * segPerBlock, litSel, segMerge, mergeBudget);
         HIPCHK(c, hipEventRecord(ev[4], c->stream2));
         // stage 3 (stream3): range coder
@@ -1010,7 +1055,7 @@ extern "C" int gc_flzma2_compress_device(gc_ctx* c, const void* d_src, size_t n,
         HIPCHK(c, hipEventRecord(ev[6], c->stream3));
         f0 = f1;
     }
-    c->mfTimed = frameBlocks > 1u; c->mfParts = nParts; c->mfPriced = c->mfTimed && c->priceParse != 0u;
+    c->mfTimed = MF_F(fArg) > 1u; c->mfParts = nParts; c->mfPriced = c->mfTimed && plan.priceParse != 0u;
     // all parts coded -> headers and assembly on the main stream
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->evPart[nParts - 1u][6], 0));
     HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
@@ -1051,19 +1096,6 @@ extern "C" int gc_flzma2_compress_host(gc_ctx* c, const void* src, size_t n, voi
 
 
 // ------------------------------------------------------------------------------------------------ BROTLI (brotli-mt framed)
-// chunk = 1 MiB x level as in brotli-mt (C/zstdmt/brotli-mt_compress.c:115-118), in 128 KiB blocks
-static uint32_t brotli_blocks_per_chunk(int level) { if (level < 1) level = 1; if (level > 11) level = 11; return (uint32_t)level * 8u; }
-
-// quality -> blocks per match-finder frame.  Quality 0: block-local finder.  Above (from quality 1 since round 3: 1.04 x the reference before): the windowed finder over frames that
-// tile the chunk exactly (a copy must not reach into the previous chunk: every chunk is a brotli stream of its own), the whole
-// chunk when it is <= 8 MiB (qualities 3-8), half of it above (72/80/88 blocks -> 36/40/44).
-static uint32_t brotli_frame_blocks(int level, uint32_t bpc)
-{
-    if (level <= 0) return 1u;
-    const uint32_t cap = level >= 7 ? GC_MF_WIDE_MAX_FRAME_BLOCKS : GC_MF_MAX_FRAME_BLOCKS;       // (qualities >= 7 run the wide geometry: 16 MiB of positions, so the 9 / 10 / 11 MiB chunks of qualities 9-11 are ONE frame since round 6)
-    return bpc <= cap ? bpc : bpc / 2u;
-}
-
 extern "C" size_t gc_brotli_compress_bound(size_t n)
 {
     const size_t nb = n ? (n + GC_ZSTD_BLOCK_MAX - 1) / GC_ZSTD_BLOCK_MAX : 1;
@@ -1089,39 +1121,12 @@ extern "C" int gc_brotli_compress_device(gc_ctx* c, const void* d_src, size_t n,
     const uint32_t nBlocks = gc_num_blocks(n);
     int rc = ensure_workspace(c, nBlocks);
     if (rc != GC_OK) return rc;
-    const uint32_t bpcFinder = brotli_blocks_per_chunk(level);
-    const uint32_t bpc = c->optBrotliPlain ? 0xFFFFFFFFu : bpcFinder;        // plain: one stream (B1 writes the stream header once, B2 / B3 no frame headers)
+    const uint32_t bpc = c->optBrotliPlain ? 0xFFFFFFFFu : brotli_blocks_per_chunk(level);     // plain: one stream (B1 writes the stream header once, B2 / B3 no frame headers)
     const uint8_t* src = (const uint8_t*)d_src;
     HIPCHK(c, hipMemsetAsync(c->brStage, 0, (size_t)nBlocks * GC_BR_STAGE_STRIDE, c->stream));
-    uint32_t frameBlocks = brotli_frame_blocks(level, bpcFinder);
-    c->lazyDepth = level >= 5 ? 2u : 1u; gc_env_u32("GC_BR_LAZY", 0u, 2u, &c->lazyDepth);        // W6 looks two positions ahead from quality 5 (round 6, emulator, 4 MiB at quality 6: web-text 0.960 -> 0.950 x the reference;
-                                                                                                  // it was 7).  W6r keeps one position (two: shared objects 1.035 -> 1.039).  Test hook
-    c->mfFast = level <= 6 ? 1u : 0u;        // (qualities 5-6 run the far pass on the fast geometry: 0.97-0.99 x the reference at 15 % less time than on the wide one)
-    // W5b from quality 7: four links (eight from quality 10) for the starts of matches in tiles with long matches, two elsewhere.  Quality 5 stays without it (round 3 measured
-    // quality 6 with (8, 0) (run r03_q3): sources 1.084 -> 1.068 x the reference and the Python library 1.024 -> 1.015, but web-text -- config C5's data, whose boilerplate
-    // makes most tiles "long" -- 16.6 -> 9.4 GB/s for 0.3 % of its size
-    // Quality 6 follows ONE link everywhere since round 4 (run r4brd / r4brd3, 64 MiB per corpus, web-text 500 MB): real Python library 1.024 -> 1.015 x the reference (inside the
-    // band), real sources 1.084 -> 1.069, shared objects 1.106 -> 1.101, web-text 17.0 -> 14.5 GB/s (W5b 5.0 ms per 500 MB).  One link for the starts of matches only:
-    // 1.020 / 1.076 / 1.104 at 15.0 GB/s; two links: 1.010 / 1.062 / 1.099 at 12.9; four (starts only beyond two): 1.009 / 1.059 / 1.098 at 11.4.  Quality 5 stays without.
-    c->searchDepth = level >= 7 ? (level >= 10 ? 8u : 4u) : (level == 6 ? 1u : 0u); c->searchShallow = c->searchDepth < 2u ? c->searchDepth : 2u;
-    if (gc_env_u32("GC_SEARCH_DEPTH", 0u, 64u, &c->searchDepth)) c->searchShallow = c->searchDepth < 2u ? c->searchDepth : 2u;      // test hook
-    gc_env_u32("GC_SEARCH_SHALLOW", 0u, 64u, &c->searchShallow);                                // test hook: links followed by the positions inside a match and in tiles without long matches
-    c->farPass = level >= 5 ? 1u : 0u; c->shortPass = 0;      // longer matches stand in for the context modelling / block splitting B1 lacks
-    gc_env_u32("GC_FAR_PASS", 0u, 1u, &c->farPass);                                            // test hook
-    c->shortPlain = 0u; c->smallWin2k = 0u; c->allLengths = 0u;
-    c->farPass2 = 0u; gc_env_u32("GC_FAR2_PASS", 0u, 1u, &c->farPass2);
-    c->ringParse = level >= 5 ? (2u | (8u << 8) | (4u << 16) | (16u << 24)) : 0u; gc_env_u32("GC_BR_RING", 0u, 0xFFFFFFFFu, &c->ringParse);
-    c->ringGeom = 256u; { uint32_t g = 0; if (gc_env_u32("GC_BR_RING_GEOM", 64u, 256u, &g) && (g & 63u) == 0u) c->ringGeom = g; }     // test hook: 64 / 128 / 256 threads = 4 / 8 / 16 sub-blocks
-    c->laneParse = level >= 7 ? 1u : 0u; gc_env_u32("GC_BR_LANE", 0u, 1u, &c->laneParse);      // qualities 7-11: W7L with the ring's first entries as its repeat distances, per block where phase A's paths repeat (launch_finder_part)
-    c->lastCodecHint = 2; c->priceMinLen = 3u; c->priceLitCtx = 0u;     // copies of >= 3 bytes (a 2-byte copy at a fresh distance never pays in brotli), one literal code per meta-block
-    c->priceParse = level >= 7 ? 1u : 0u;         // (quality 7 since round 6 -- emulator, 2 MiB, with W7L: real sources 1.018 -> 0.980 x the reference, shared objects 1.040 -> 1.026, text 0.963 -> 0.939.)
-                                                  // The reference parses greedily up to quality 9 (zopfli from 10).  Measured at quality 6
-                                                  // (run 28, 64 MiB per corpus): greedy + far pass 0.979-1.002 x the reference at 16.6 GB/s,
-                                                  // price-based parse without far pass 0.983-1.012 x at 11.1 GB/s, both 0.93-0.98 x at 9.4 GB/s
-    gc_env_u32("GC_PRICE_PARSE", 0u, 1u, &c->priceParse);                                      // test hook
-    if (frameBlocks > nBlocks) frameBlocks = nBlocks;                       // short input: one chunk, one frame
+    const GcLzPlan plan = with_hooks(brotli_plan(level));
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-    rc = launch_finder(c, src, n, frameBlocks, nullptr);
+    rc = launch_finder(c, plan, src, n, lz_frame_arg(GC_CODEC_BROTLI, level, nBlocks, 0u), nullptr);
     if (rc != GC_OK) return rc;
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     uint32_t brRepSub = 2u;                                    // B1's last-distance substitution (gc_brotli.hip): two passes.  Emulator, quality 6, x the reference, passes 0 / 1 / 2 / 3 / 4: shared objects
@@ -1254,17 +1259,8 @@ extern "C" void gc_host_free(void* p) { if (p) hipHostFree(p); }
 // dictionary reset (FLZMA2: match-finder frames).  Host schedulers split the input at multiples of it.
 extern "C" size_t gc_codec_grain(int codec, int level)
 {
-    uint32_t fb = codec == GC_CODEC_ZSTD ? zstd_frame_blocks(level) : flzma2_frame_blocks(level);
-    if (codec != GC_CODEC_BROTLI && fb > 1u) gc_env_u32("GC_FRAME_BLOCKS", 1u, GC_MF_MAX_FRAME_BLOCKS, &fb);     // test hook: small frames (as in gc_ctx_create)
-    if (codec != GC_CODEC_BROTLI && fb > 1u) {                                                                   // overlapping frames: the unit is the group (zstd 16-22: 32 MiB, FLZMA2 5-6: 16 MiB, 7-9: 64 MiB)
-        uint32_t grp = codec == GC_CODEC_ZSTD ? zstd_group_blocks(level) : flzma2_group_blocks(level);
-        const bool grpHook = gc_env_u32("GC_MF_GROUP", 1u, 65535u, &grp);                                        // test hooks, read as the compress paths read them (small overlapping frames: shards must not cut a group)
-        uint32_t stride = codec == GC_CODEC_ZSTD ? zstd_stride_blocks(level) : flzma2_stride_blocks(level); gc_env_u32("GC_MF_STRIDE", 1u, GC_MF_MAX_FRAME_BLOCKS, &stride);
-        const uint32_t fbDefault = codec == GC_CODEC_ZSTD ? zstd_frame_blocks(level) : flzma2_frame_blocks(level);
-        if (grp > fb && (fb == fbDefault || grpHook) && stride < fb && (fb % stride) == 0u && ((grp - fb) % stride) == 0u) fb = grp;
-    }
-    if (codec != GC_CODEC_BROTLI) return (size_t)fb * GC_ZSTD_BLOCK_MAX;
-    return (size_t)brotli_blocks_per_chunk(level) * GC_ZSTD_BLOCK_MAX;
+    if (codec == GC_CODEC_BROTLI) return (size_t)brotli_blocks_per_chunk(level) * GC_ZSTD_BLOCK_MAX;
+    return (size_t)MF_C(lz_frame_arg(codec, level, UINT32_MAX, dbg_frame_blocks())) * GC_ZSTD_BLOCK_MAX;     // overlapping frames: the unit is the group (zstd 16-22: 32 MiB, FLZMA2 5-6: 16 MiB, 7-9: 64 MiB)
 }
 
 // ---------------------------------------------------------------- ZSTD decoding ----------------------------------------------------------------
@@ -1414,7 +1410,6 @@ extern "C" int gc_zstd_decompress_device(gc_ctx* c, const void* d_src, size_t n,
 #ifdef HIPEMU
         overlap = false;
 #endif
-        { uint32_t v = 0; if (gc_env_u32("GC_ZD_OVERLAP", 0, 1, &v)) overlap = overlap && v != 0u; }
         if (serialRetry) overlap = false;
         // The wide execution (all blocks of all frames at once through byte pointers and pointer jumping, see gc_zstd_dec.hip) instead of one workgroup
         // per frame that copies its blocks in order (~0.27 GB/s per frame): 1 GB in 120 frames 13.7 ms against 49 ms, and it does not care how few
