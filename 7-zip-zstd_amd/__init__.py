@@ -32,7 +32,8 @@ EXPORTS = ["gc_test_hooks_enabled", "gc_lzfind_get_matches_device", "gc_device_c
            "gc_host_alloc", "gc_host_free", "gc_multi_create", "gc_multi_destroy", "gc_multi_workers", "gc_multi_last_error",
            "gc_multi_piece_bytes", "gc_multi_compress_host",
            "gc_bra_convert_device", "gc_bra_x86_convert_device", "gc_delta_convert_device", "gc_zstd_scan_frames", "gc_zstd_scan_prefix", "gc_zstd_decompress_device", "gc_zstd_decompress_host", "gc_zstd_decompress_timing", "gc_zstd_decompress_kernel_timing", "gc_zstd_decompress_wide_rounds", "gc_zstd_decompress_selfcheck", "gc_filter_host",
-           "gc_brotli_scan_prefix", "gc_brotli_dec_set_dictionary", "gc_brotli_dec_has_dictionary", "gc_brotli_decompress_device", "gc_brotli_decompress_host", "gc_brotli_decompress_timing"]
+           "gc_brotli_scan_prefix", "gc_brotli_dec_set_dictionary", "gc_brotli_dec_has_dictionary", "gc_brotli_decompress_device", "gc_brotli_decompress_host", "gc_brotli_decompress_timing",
+           "gc_lzma2_scan_prefix", "gc_lzma2_decompress_device", "gc_lzma2_decompress_host", "gc_lzma2_decompress_timing"]
 
 CODEC_ZSTD, CODEC_FLZMA2, CODEC_BROTLI = 0, 1, 2
 CODEC_IDS = {"zstd": CODEC_ZSTD, "flzma2": CODEC_FLZMA2, "brotli": CODEC_BROTLI}
@@ -154,6 +155,14 @@ def load_library(path=None):
     lib.gc_brotli_decompress_host.restype = C.c_int
     lib.gc_brotli_decompress_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     lib.gc_brotli_decompress_timing.restype = C.c_int
+    lib.gc_lzma2_scan_prefix.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    lib.gc_lzma2_scan_prefix.restype = C.c_int
+    lib.gc_lzma2_decompress_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_ubyte, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.gc_lzma2_decompress_device.restype = C.c_int
+    lib.gc_lzma2_decompress_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_ubyte, C.POINTER(C.c_size_t)]
+    lib.gc_lzma2_decompress_host.restype = C.c_int
+    lib.gc_lzma2_decompress_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    lib.gc_lzma2_decompress_timing.restype = C.c_int
     return lib
 
 
@@ -202,6 +211,11 @@ class ZstdFrame(C.Structure):
 class BrotliChunk(C.Structure):
     """gc_brotli_chunk of include/gpucodec.h"""
     _fields_ = [("src_off", C.c_uint64), ("src_size", C.c_uint32), ("capacity", C.c_uint32)]
+
+
+class Lzma2Unit(C.Structure):
+    """gc_lzma2_unit of include/gpucodec.h"""
+    _fields_ = [("src_off", C.c_uint64), ("src_size", C.c_uint64), ("dst_off", C.c_uint64), ("dst_size", C.c_uint64), ("n_chunks", C.c_uint32), ("flags", C.c_uint32)]
 
 
 def crc32_device(ptr, n, lib_path=None):
@@ -504,6 +518,46 @@ class BrotliDecoder(_EncoderBase):
     def last_timing_ms(self):
         ms = C.c_float(0)
         self._check(self._lib.gc_brotli_decompress_timing(self._ctx, C.byref(ms)), "gc_brotli_decompress_timing")
+        return float(ms.value)
+
+
+class Lzma2Decoder(_EncoderBase):
+    """Mirror of NCompress::NLzma2::CDecoder (CPP/7zip/Compress/Lzma2Decoder.cpp) for whole LZMA2 chunk streams: one wave per unit (a run of chunks that starts with a
+    dictionary reset) on the GPU.  `prop` is the coder's one property byte (Flzma2Encoder.coder_props()[0])."""
+
+    def scan(self, data):
+        """-> (array of Lzma2Unit, their number, the sum of their contents, bytes of the whole units (and the end marker), whether the end marker was reached)"""
+        import numpy as np
+        a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+        n = C.c_size_t(0); used = C.c_size_t(0); total = C.c_uint64(0); ended = C.c_int(0)
+        rc = self._lib.gc_lzma2_scan_prefix(a.ctypes.data, a.size, None, 0, C.byref(n), None, None, None)
+        if rc != GC_OK:
+            raise GpuCodecError("gc_lzma2_scan_prefix failed: %s" % _ERR.get(rc, rc))
+        units = (Lzma2Unit * max(1, n.value))()
+        rc = self._lib.gc_lzma2_scan_prefix(a.ctypes.data, a.size, units, n.value, C.byref(n), C.byref(total), C.byref(used), C.byref(ended))
+        if rc != GC_OK:
+            raise GpuCodecError("gc_lzma2_scan_prefix failed: %s" % _ERR.get(rc, rc))
+        return units, n.value, total.value, used.value, bool(ended.value)
+
+    def code(self, data, prop, capacity=None):
+        """LZMA2 stream (ending with 0x00) -> numpy uint8 content (host buffers; includes PCIe copies).  capacity: the scan's exact total unless given."""
+        import numpy as np
+        a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+        if capacity is None:
+            capacity = self.scan(a)[2]
+        out = np.empty(max(1, capacity), dtype=np.uint8)
+        n = C.c_size_t(0)
+        self._check(self._lib.gc_lzma2_decompress_host(self._ctx, a.ctypes.data, a.size, out.ctypes.data, capacity, int(prop), C.byref(n)), "gc_lzma2_decompress_host")
+        return out[:n.value]
+
+    def code_device(self, d_src_ptr, n, d_dst_ptr, dst_cap, prop, units, n_units):
+        size = C.c_size_t(0)
+        self._check(self._lib.gc_lzma2_decompress_device(self._ctx, d_src_ptr, n, d_dst_ptr, dst_cap, int(prop), units, n_units, C.byref(size)), "gc_lzma2_decompress_device")
+        return size.value
+
+    def last_timing_ms(self):
+        ms = C.c_float(0)
+        self._check(self._lib.gc_lzma2_decompress_timing(self._ctx, C.byref(ms)), "gc_lzma2_decompress_timing")
         return float(ms.value)
 
 

@@ -11,6 +11,7 @@
 #include "gc_mf.h"
 #include "gc_zstd_dec.h"
 #include "gc_brotli_dec.h"
+#include "gc_lzma2_dec_work.h"
 #ifdef HIPEMU
 #include "hip_runtime_stub.h"
 #else
@@ -139,6 +140,7 @@ struct gc_ctx {
     uint64_t* hostResult;     // pinned
     // staging for the host-buffer entry point
     GcBrDecWork brd;          // BROTLI decoder (gc_brotli_dec.hip)
+    GcL2dWork l2d;            // LZMA2 decoder (gc_lzma2_dec.h)
     uint8_t* dIn; size_t dInCap; uint8_t* dOut; size_t dOutCap; uint8_t* dPre; size_t dPreCap;      // (dPre: the pre-filtered input of gc_host_begin_pre)
     bool pending; bool timed;
     // zstd decoder (gc_zstd_dec.hip): per-workgroup literal / sequence workspace, frame table, per-frame results, ticket counter
@@ -190,6 +192,9 @@ extern "C" size_t gc_zstd_compress_bound(size_t n)
 static void free_workspace(gc_ctx* c);
 void gc_brd_release(GcBrDecWork* w);
 int gc_brd_decode(hipStream_t st, GcBrDecWork* w, const uint8_t* d_src, const gc_brotli_chunk* chunks, size_t nChunks, uint8_t* d_dst, size_t dstCap, size_t* produced, char* err, size_t errCap);
+void gc_l2d_release(GcL2dWork* w);
+int gc_l2d_decode(hipStream_t st, GcL2dWork* w, const uint8_t* d_src, size_t n, const gc_lzma2_unit* units, size_t nUnits, uint8_t* d_dst, size_t dstCap, unsigned dictProp,
+                  size_t* produced, char* err, size_t errCap);
 static void ctx_release(gc_ctx* c);
 
 extern "C" int gc_ctx_create(gc_ctx** out, int device)
@@ -221,6 +226,7 @@ extern "C" int gc_ctx_create(gc_ctx** out, int device)
     if (rc == GC_OK && (hipMalloc((void**)&c->result, 16) != hipSuccess || hipHostMalloc((void**)&c->hostResult, 16 + GC_MAX_PARTS * 16u * sizeof(uint32_t)) != hipSuccess)) rc = GC_ERR_NOMEM;      // (+ a copy of the ticket / watchdog words)
     if (rc != GC_OK) { ctx_release(c); return rc; }
     c->dbgFrameBlocks = dbg_frame_blocks(); c->dbgPartFrames = 0;
+    c->l2d.nCU = c->nCU;
     gc_env_u32("GC_PART_FRAMES", 1u, 1u << 20, &c->dbgPartFrames);                      // test hook: small parts
     *out = c;
     return GC_OK;
@@ -244,6 +250,7 @@ static void ctx_release(gc_ctx* c)
     free_workspace(c);
     hipFree(c->prof); hipFree(c->mfTicket); hipFree(c->result); if (c->hostResult) hipHostFree(c->hostResult); hipFree(c->dIn); hipFree(c->dOut); hipFree(c->dPre);
     gc_brd_release(&c->brd);
+    gc_l2d_release(&c->l2d);
     hipFree(c->zdLit); hipFree(c->zdSeq); hipFree(c->zdFrames); hipFree(c->zdResult); hipFree(c->zdTot); hipFree(c->zdBlocks); hipFree(c->zdOrder); hipFree(c->zdReady); hipFree(c->zdTicket); hipFree(c->zdPlace); hipFree(c->zdPtr); hipFree(c->zdDone); hipFree(c->zdFerr);
     for (int i = 0; i < 2; i++) if (c->zdEv[i]) hipEventDestroy(c->zdEv[i]);
     hipFree(c->mfTileWord); hipFree(c->mfCnt); hipFree(c->mfEnt); hipFree(c->mfEnt2); hipFree(c->mfRec); hipFree(c->mfRec2); hipFree(c->mfChanged); hipFree(c->mfRec3); hipFree(c->mfDp); hipFree(c->mfPrice); hipFree(c->mfWinCost); hipFree(c->mfDpStat); hipFree(c->mfLitPrice);
@@ -1660,3 +1667,41 @@ extern "C" int gc_brotli_decompress_host(gc_ctx* c, const void* src, size_t n, v
     return rc;
 }
 extern "C" int gc_brotli_decompress_timing(gc_ctx* c, float* ms) { if (!c || !ms) return GC_ERR_PARAM; *ms = c->brd.ms; return GC_OK; }
+
+// ---- LZMA2 decoder (gc_lzma2_dec.h): the context's stream and buffers around gc_l2d_decode
+static void l2d_hooks(gc_ctx* c) { uint32_t v = 0; gc_env_u32("GC_L2D_INSTANCE", 1u, 2u, &v); c->l2d.instance = v; }      // test hook: one kernel instance for every unit
+extern "C" int gc_lzma2_decompress_device(gc_ctx* c, const void* d_src, size_t n, void* d_dst, size_t dstCap, unsigned char dictProp, const gc_lzma2_unit* units, size_t nUnits, size_t* outSize)
+{
+    if (!c || (!d_src && n) || (!units && nUnits) || !outSize) return GC_ERR_PARAM;
+    HIPCHK(c, hipSetDevice(c->device));
+    *outSize = 0;
+    l2d_hooks(c);
+    return gc_l2d_decode(c->stream, &c->l2d, (const uint8_t*)d_src, n, units, nUnits, (uint8_t*)d_dst, dstCap, dictProp, outSize, c->err, sizeof(c->err));
+}
+extern "C" int gc_lzma2_decompress_host(gc_ctx* c, const void* src, size_t n, void* dst, size_t dstCap, unsigned char dictProp, size_t* outSize)
+{
+    if (!c || (!src && n) || (!dst && dstCap) || dictProp > 40) return GC_ERR_PARAM;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (outSize) *outSize = 0;
+    size_t nUnits = 0, consumed = 0; int ended = 0; uint64_t total = 0;
+    int rc = gc_lzma2_scan_prefix(src, n, nullptr, 0, &nUnits, &total, &consumed, &ended);
+    if (rc == GC_OK && !ended) rc = GC_ERR_CORRUPT;               // the input ends inside a unit, or without the end marker
+    if (rc != GC_OK) { snprintf(c->err, sizeof(c->err), "not a whole LZMA2 stream (chunk scan failed)"); return rc; }
+    if (total > dstCap) { snprintf(c->err, sizeof(c->err), "destination too small: need %llu bytes", (unsigned long long)total); return GC_ERR_DST_SMALL; }
+    c->l2d.ms = 0.0f;
+    if (!nUnits) return GC_OK;
+    gc_lzma2_unit* un = (gc_lzma2_unit*)malloc(nUnits * sizeof(gc_lzma2_unit));
+    if (!un) return GC_ERR_NOMEM;
+    rc = gc_lzma2_scan_prefix(src, n, un, nUnits, &nUnits, &total, &consumed, &ended);
+    if (rc == GC_OK && consumed > c->dInCap) { hipFree(c->dIn); c->dIn = nullptr; c->dInCap = 0; if (hipMalloc((void**)&c->dIn, consumed + 64) != hipSuccess) rc = GC_ERR_NOMEM; else c->dInCap = consumed; }
+    if (rc == GC_OK && total > c->dOutCap) { hipFree(c->dOut); c->dOut = nullptr; c->dOutCap = 0; if (hipMalloc((void**)&c->dOut, (size_t)total + 64) != hipSuccess) rc = GC_ERR_NOMEM; else c->dOutCap = (size_t)total; }
+    size_t produced = 0;
+    if (rc == GC_OK && hipMemcpyAsync(c->dIn, src, consumed, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = GC_ERR_HIP;
+    l2d_hooks(c);
+    if (rc == GC_OK) rc = gc_l2d_decode(c->stream, &c->l2d, c->dIn, consumed, un, nUnits, c->dOut, (size_t)total, dictProp, &produced, c->err, sizeof(c->err));
+    if (rc == GC_OK && produced && (hipMemcpyAsync(dst, c->dOut, produced, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) rc = GC_ERR_HIP;
+    free(un);
+    if (rc == GC_OK && outSize) *outSize = produced;
+    return rc;
+}
+extern "C" int gc_lzma2_decompress_timing(gc_ctx* c, float* ms) { if (!c || !ms) return GC_ERR_PARAM; *ms = c->l2d.ms; return GC_OK; }

@@ -105,3 +105,6 @@ gc_lzma2_emit_kernel(const uint8_t* __restrict__ src, uint32_t segLog, const uin
         for (uint32_t i = t; i < ci.usize; i += 256u) o[3u + i] = s[i];
     }
 }
+
+// The LZMA2 DECODER (kernels and host side) reaches the product and the emulator build through this unit.
+#include "gc_lzma2_dec.h"

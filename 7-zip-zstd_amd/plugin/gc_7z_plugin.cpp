@@ -33,7 +33,7 @@
 namespace {
 
 struct MethodInfo { uint64_t id; const char* name; int kind; int filter; /* -1: a codec; else the gc_filter_host kind of a pre-filter (round 3) */ unsigned align; };
-enum { KIND_ZSTD = 0, KIND_FLZMA2 = 1, KIND_BROTLI = 2, KIND_FILTER = 3 };
+enum { KIND_ZSTD = 0, KIND_FLZMA2 = 1, KIND_BROTLI = 2, KIND_FILTER = 3, KIND_LZMA2_DEC = 4 };
 // Names and ids as registered by the reference (CPP/7zip/Compress/ZstdRegister.cpp:13-17, FastLzma2Register.cpp:13-18,
 // BrotliRegister.cpp:13-17).  A host that has these codecs built in (the reference's own 7z.so) resolves a method NAME to its
 // built-in encoder first (FindMethod_Index, CPP/7zip/Common/CreateCoder.cpp:160-204), so every method is registered a second
@@ -58,6 +58,9 @@ const MethodInfo kMethods[] = {
     { 0xA, "ARM64GPU", KIND_FILTER, GC_BRA_ARM64, 3 },
     { 0xB, "RISCVGPU", KIND_FILTER, GC_BRA_RISCV, 1 },
     { 3, "DELTAGPU", KIND_FILTER, GC_FILTER_DELTA, 0 },
+    // LZMA2 DECODER only (id 0x21), a row of its own at the end so that no index above moves: FLZMA2 / FLZMA2GPU stay encoder rows.  A host looks a method id up among
+    // its built-in codecs first and every stock 7-Zip has LZMA2 built in, so this decoder is chosen only by a host built without one.
+    { 0x21, "LZMA2GPU", KIND_LZMA2_DEC, -1, 0 },
 };
 const uint32_t kNumMethods = sizeof(kMethods) / sizeof(kMethods[0]);
 
@@ -638,6 +641,129 @@ public:
     }
 };
 
+// LZMA2 decoder (NCompress::NLzma2::CDecoder, CPP/7zip/Compress/Lzma2Decoder.cpp; C/Lzma2Dec.c): the input is read in large pieces; every piece is cut at the end of its last
+// whole UNIT (gc_lzma2_scan_prefix: a run of chunks from one dictionary reset to the next), those units are decoded on the GPU (one wave per unit), the content is
+// written out in order, the tail moves to the front.  A unit larger than the buffer grows the buffer.  The stream ends at the end marker 0x00; what lies behind it is not read
+// as LZMA2.  The one property byte is the dictionary size (Lzma2Decoder.cpp SetDecoderProperties2: exactly one byte).
+class CGpuLzma2Decoder final : public ICompressCoder, public ICompressSetDecoderProperties2, public ICompressSetCoderMt {
+    ULONG refs_ = 1;
+    gc_lzma2_unit* units_ = nullptr; size_t unitsCap_ = 0;
+    uint8_t prop_ = 40;                                          // (no props: the format's largest dictionary, i.e. no bound beyond the bytes since the reset)
+
+public:
+    ~CGpuLzma2Decoder() { free(units_); }
+
+    HRESULT QueryInterface(const GUID& iid, void** out) override
+    {
+        if (!out) return E_INVALIDARG;
+        *out = nullptr;
+        if (iid == IID_IUnknown || iid == IID_ICompressCoder) *out = static_cast<ICompressCoder*>(this);
+        else if (iid == IID_ICompressSetDecoderProperties2) *out = static_cast<ICompressSetDecoderProperties2*>(this);
+        else if (iid == IID_ICompressSetCoderMt) *out = static_cast<ICompressSetCoderMt*>(this);
+        else return E_NOINTERFACE;
+        ++refs_;
+        return S_OK;
+    }
+    ULONG AddRef() override { return ++refs_; }
+    ULONG Release() override { if (--refs_ != 0) return refs_; delete this; return 0; }
+
+    HRESULT SetNumberOfThreads(uint32_t) override { return S_OK; }
+    HRESULT SetDecoderProperties2(const uint8_t* data, uint32_t size) override
+    {
+        if (size != 1) return E_NOTIMPL;
+        if (!data || data[0] > 40) return E_NOTIMPL;              // (Lzma2Dec_GetOldProps: SZ_ERROR_UNSUPPORTED)
+        prop_ = data[0];
+        return S_OK;
+    }
+
+    HRESULT Code(ISequentialInStream* in, ISequentialOutStream* out, const uint64_t*, const uint64_t* outSize, ICompressProgressInfo* progress) override
+    {
+        if (!in || !out) return E_INVALIDARG;
+        gc_ctx* const ctx = shared_dec_ctx();
+        if (!ctx) return E_FAIL;                                                               // no gfx950 device: there is no CPU decoder behind this object
+        BufLease lease;
+        uint8_t*& inBuf_ = lease.b.in[0]; size_t& inCap_ = lease.b.inCap[0]; uint8_t*& outBuf_ = lease.b.out; size_t& outCap_ = lease.b.outCap;
+        const size_t kPiece = (size_t)64 << 20;
+        const size_t kMaxIn = (size_t)1 << 30;               // largest compressed unit buffered whole
+        const size_t kMaxContent = (size_t)4 << 30;          // largest content of one piece
+        if (!buf_grow(&inBuf_, &inCap_, kPiece, 0)) return E_OUTOFMEMORY;
+        uint64_t totalIn = 0, totalOut = 0;
+        size_t have = 0;
+        bool eof = false, ended = false;
+        while (!ended) {
+            while (!eof && have < inCap_) {
+                const size_t want = inCap_ - have;
+                size_t got = want;
+                HRESULT r = read_full(in, inBuf_ + have, &got);
+                if (r != S_OK) return r;
+                have += got; totalIn += got;
+                if (got < want) eof = true;
+            }
+            size_t nUnits = 0, consumed = 0; int end = 0;
+            int rc = gc_lzma2_scan_prefix(inBuf_, have, nullptr, 0, &nUnits, nullptr, &consumed, &end);
+            if (rc != GC_OK) return E_FAIL;
+            if (consumed == 0) {                                   // not even one whole unit in the buffer
+                if (eof) return E_FAIL;                            // the stream ends inside a unit, or without its end marker
+                if (inCap_ >= kMaxIn) return E_NOTIMPL;
+                if (!buf_grow(&inBuf_, &inCap_, inCap_ * 2u, have)) return E_OUTOFMEMORY;
+                continue;
+            }
+            size_t produced = 0;
+            if (nUnits) {
+                if (nUnits > unitsCap_) {
+                    free(units_); unitsCap_ = 0;
+                    units_ = (gc_lzma2_unit*)malloc((nUnits + 64u) * sizeof(gc_lzma2_unit));
+                    if (!units_) return E_OUTOFMEMORY;
+                    unitsCap_ = nUnits + 64u;
+                }
+                rc = gc_lzma2_scan_prefix(inBuf_, have, units_, unitsCap_, &nUnits, nullptr, &consumed, &end);
+                if (rc != GC_OK) return E_FAIL;
+                // a piece whose units hold more than kMaxContent (or more than a call takes) is decoded a run of units at a time; one unit beyond it is refused
+                size_t cap = 0, take = 0;
+                for (; take < nUnits && take < ((size_t)1 << 20); take++) {
+                    if (units_[take].dst_size > kMaxContent) return E_NOTIMPL;
+                    if (cap + units_[take].dst_size > kMaxContent) break;
+                    cap += (size_t)units_[take].dst_size;
+                }
+                if (take < nUnits) { consumed = (size_t)units_[take].src_off; end = 0; }
+                if (!buf_grow(&outBuf_, &outCap_, cap ? cap : 1u, 0)) return E_OUTOFMEMORY;
+                std::lock_guard<std::mutex> g(shared()->gpu);
+                // (units as the scan placed them: dst_off counts from the piece's first unit; the device entry copies what the units cover)
+                rc = lzma2_units_host(ctx, inBuf_, consumed, units_, take, outBuf_, cap, prop_, &produced);
+                if (rc != GC_OK) return rc == GC_ERR_UNSUPPORTED ? E_NOTIMPL : hresult_of(rc);
+            }
+            HRESULT r = write_all(out, outBuf_, produced);
+            if (r != S_OK) return r;
+            totalOut += produced;
+            have -= consumed;
+            if (have) memmove(inBuf_, inBuf_ + consumed, have);
+            ended = end != 0;
+            if (progress) {
+                const uint64_t pin = totalIn - have;
+                r = progress->SetRatioInfo(&pin, &totalOut);
+                if (r != S_OK) return r;
+            }
+        }
+        if (outSize && *outSize != totalOut) return E_FAIL;       // the folder's unpack size and the stream disagree
+        return S_OK;
+    }
+
+private:
+    // the run of whole units at the front of a host buffer: a stream of its own once an end marker stands behind it
+    static int lzma2_units_host(gc_ctx* ctx, uint8_t* buf, size_t n, const gc_lzma2_unit* units, size_t nUnits, uint8_t* dst, size_t cap, uint8_t prop, size_t* produced)
+    {
+        *produced = 0;
+        if (nUnits == 0) return GC_OK;
+        const size_t end = (size_t)(units[nUnits - 1].src_off + units[nUnits - 1].src_size);      // <= n; the byte there is the next control byte (or lies behind the buffer's data)
+        if (end >= n + 1u) return GC_ERR_PARAM;
+        const uint8_t keep = buf[end];
+        buf[end] = 0x00;
+        const int rc = gc_lzma2_decompress_host(ctx, buf, end + 1u, dst, cap, prop, produced);
+        buf[end] = keep;
+        return rc;
+    }
+};
+
 // A pre-filter object: NCompress::NBranch::CCoder / CEncoder / CDecoder (BranchMisc.cpp:14-118), NCompress::NBcj::CCoder2 (BcjCoder.cpp:10-22) and
 // NCompress::NDelta::CEncoder / CDecoder (DeltaFilter.cpp:28-119) over gc_filter_host: every Filter() call takes the host's buffer to the device, converts it
 // there and brings it back; the program counter, the x86 converter's state word and the Delta filter's 256 bytes of history are carried from call to call.
@@ -739,10 +865,11 @@ HRESULT create_decoder(uint32_t index, const GUID* iid, void** out)
     if (!out) return E_INVALIDARG;
     *out = nullptr;
     if (index < kNumMethods && kMethods[index].kind == KIND_FILTER) return create_filter(index, false, iid, out);
-    if (index >= kNumMethods || (kMethods[index].kind != KIND_ZSTD && kMethods[index].kind != KIND_BROTLI)) return CLASS_E_CLASSNOTAVAILABLE;     // (FLZMA2: the host's LZMA2 decoder)
+    if (index >= kNumMethods || (kMethods[index].kind != KIND_ZSTD && kMethods[index].kind != KIND_BROTLI && kMethods[index].kind != KIND_LZMA2_DEC)) return CLASS_E_CLASSNOTAVAILABLE;     // (FLZMA2 / FLZMA2GPU are encoder rows: LZMA2GPU is the decoder's)
     if (!iid || !(*iid == IID_ICompressCoder)) return E_NOINTERFACE;
     IUnknown* obj = nullptr;
     if (kMethods[index].kind == KIND_BROTLI) { CGpuBrotliDecoder* d = new (std::nothrow) CGpuBrotliDecoder(); obj = d ? static_cast<ICompressCoder*>(d) : nullptr; }
+    else if (kMethods[index].kind == KIND_LZMA2_DEC) { CGpuLzma2Decoder* d = new (std::nothrow) CGpuLzma2Decoder(); obj = d ? static_cast<ICompressCoder*>(d) : nullptr; }
     else { CGpuZstdDecoder* d = new (std::nothrow) CGpuZstdDecoder(); obj = d ? static_cast<ICompressCoder*>(d) : nullptr; }
     if (!obj) return E_OUTOFMEMORY;
     *out = obj;
@@ -753,7 +880,7 @@ HRESULT create_encoder(uint32_t index, const GUID* iid, void** out)
 {
     if (!out) return E_INVALIDARG;
     *out = nullptr;
-    if (index >= kNumMethods) return CLASS_E_CLASSNOTAVAILABLE;
+    if (index >= kNumMethods || kMethods[index].kind == KIND_LZMA2_DEC) return CLASS_E_CLASSNOTAVAILABLE;     // (LZMA2GPU: a decoder-only row)
     if (kMethods[index].kind == KIND_FILTER) return create_filter(index, true, iid, out);
     if (!iid || !(*iid == IID_ICompressCoder)) return E_NOINTERFACE;     // the 1-stream codecs (CodecExports.cpp:127-150)
     warm_up_async();                                       // the devices are opened while the host sets the coder up and reads its first input
@@ -778,17 +905,18 @@ GC_EXPORT HRESULT GetMethodProperty(uint32_t index, PROPID propID, PROPVARIANT* 
         case NMethodPropID::kID: value->vt = VT_UI8; value->uhVal = m.id; break;
         case NMethodPropID::kName: value->bstrVal = gc_bstr_ascii(m.name); if (!value->bstrVal) return E_OUTOFMEMORY; value->vt = VT_BSTR; break;
         case NMethodPropID::kEncoder: {
+            if (m.kind == KIND_LZMA2_DEC) break;
             GUID g = gc_codec_clsid(m.id, true);
             value->bstrVal = gc_bstr_bytes(&g, sizeof(g)); if (!value->bstrVal) return E_OUTOFMEMORY; value->vt = VT_BSTR; break;
         }
-        case NMethodPropID::kEncoderIsAssigned: value->vt = VT_BOOL; value->boolVal = -1; break;   // VARIANT_TRUE
+        case NMethodPropID::kEncoderIsAssigned: value->vt = VT_BOOL; value->boolVal = m.kind == KIND_LZMA2_DEC ? 0 : -1; break;   // VARIANT_TRUE but for the decoder-only row
         case NMethodPropID::kDecoder:
-            if (m.kind == KIND_ZSTD || m.kind == KIND_BROTLI || m.kind == KIND_FILTER) {
+            if (m.kind == KIND_ZSTD || m.kind == KIND_BROTLI || m.kind == KIND_FILTER || m.kind == KIND_LZMA2_DEC) {
                 GUID g = gc_codec_clsid(m.id, false);
                 value->bstrVal = gc_bstr_bytes(&g, sizeof(g)); if (!value->bstrVal) return E_OUTOFMEMORY; value->vt = VT_BSTR;
             }
             break;
-        case NMethodPropID::kDecoderIsAssigned: value->vt = VT_BOOL; value->boolVal = (m.kind == KIND_ZSTD || m.kind == KIND_BROTLI || m.kind == KIND_FILTER) ? -1 : 0; break;
+        case NMethodPropID::kDecoderIsAssigned: value->vt = VT_BOOL; value->boolVal = (m.kind == KIND_ZSTD || m.kind == KIND_BROTLI || m.kind == KIND_FILTER || m.kind == KIND_LZMA2_DEC) ? -1 : 0; break;
         case NMethodPropID::kIsFilter: value->vt = VT_BOOL; value->boolVal = m.kind == KIND_FILTER ? -1 : 0; break;
         default: break;      // kPackStreams, ...: left VT_EMPTY
     }
@@ -805,9 +933,9 @@ GC_EXPORT HRESULT CreateObject(const GUID* clsid, const GUID* iid, void** out)
     *out = nullptr;
     if (!clsid) return E_INVALIDARG;
     for (uint32_t i = 0; i < kNumMethods; i++)
-        if (*clsid == gc_codec_clsid(kMethods[i].id, true)) return create_encoder(i, iid, out);
+        if (kMethods[i].kind != KIND_LZMA2_DEC && *clsid == gc_codec_clsid(kMethods[i].id, true)) return create_encoder(i, iid, out);
     for (uint32_t i = 0; i < kNumMethods; i++)
-        if ((kMethods[i].kind == KIND_ZSTD || kMethods[i].kind == KIND_BROTLI || kMethods[i].kind == KIND_FILTER) && *clsid == gc_codec_clsid(kMethods[i].id, false)) return create_decoder(i, iid, out);
+        if ((kMethods[i].kind == KIND_ZSTD || kMethods[i].kind == KIND_BROTLI || kMethods[i].kind == KIND_FILTER || kMethods[i].kind == KIND_LZMA2_DEC) && *clsid == gc_codec_clsid(kMethods[i].id, false)) return create_decoder(i, iid, out);
     return CLASS_E_CLASSNOTAVAILABLE;
 }
 

@@ -308,6 +308,36 @@ int         gc_brotli_decompress_host(gc_ctx* ctx, const void* src, size_t n, vo
 /* HIP-event duration of the decode kernels of the last gc_brotli_decompress_* call */
 int         gc_brotli_decompress_timing(gc_ctx* ctx, float* ms);
 
+/* ---- LZMA2 decoding on the device (7-Zip method id 0x21).  Replaces NCompress::NLzma2::CDecoder (CPP/7zip/Compress/Lzma2Decoder.cpp) and the
+ * Lzma2Dec_DecodeToDic / LzmaDec_DecodeReal loops under it (C/Lzma2Dec.c, C/LzmaDec.c) for callers that hold whole units of an LZMA2 chunk stream -- this engine's
+ * FLZMA2 streams, Fast-LZMA2's, mainline 7-Zip's and xz's raw LZMA2 alike.  A UNIT is a run of chunks that starts with a dictionary reset (control 0x01 or >= 0xE0)
+ * and ends in front of the next one or of the end marker 0x00: units are independent of each other (the split C/Lzma2DecMt.c makes for its threads), chunks inside a
+ * unit are not.  One wave per unit; a stream without inner dictionary resets is ONE unit and runs on one wave.
+ *   gc_lzma2_scan_prefix         host: walks the chunk headers (no payload is read).  units may be NULL to count.  An input that ends inside a unit is not an error:
+ *                                *consumed = the bytes of the whole units (a unit is whole once the next dictionary reset or the end marker has been seen), plus the end
+ *                                marker when it was reached (*ended = 1; bytes behind it are not consumed).  dst_size is EXACT (the sum of the chunks' unpacked sizes),
+ *                                dst_off the prefix sum over the units, *contentTotal their sum.  GC_ERR_CORRUPT: a control byte 0x03..0x7F, a first chunk that does not
+ *                                reset the dictionary, an LZMA chunk without props where its unit has had none yet, a props byte >= 225 or with lc + lp > 4.
+ *   gc_lzma2_decompress_device   units as the scan returned them (host memory), d_src / d_dst device memory; every unit's content goes to d_dst + dst_off.
+ *                                dictProp: the coder's one property byte (gc_flzma2_dict_prop; LZMA2_DIC_SIZE_FROM_PROP, C/Lzma2Dec.c), > 40 is GC_ERR_PARAM; a stream
+ *                                made of several streams is decoded with the largest of their bytes.  At most 2^20 units per call, each below 4 GiB - 64 KiB.
+ *                                *decompressedSize = the sum of the units' contents.  Workspace and stream: the context's, as for gc_brotli_decompress_device.
+ *   gc_lzma2_decompress_host     scan + H2D + decode + D2H; the stream must end with 0x00 (else GC_ERR_CORRUPT).
+ * GC_ERR_CORRUPT: damaged stream (what Lzma2Dec.c / LzmaDec.c refuse: a first range-coder byte that is not 0, a distance beyond the bytes since the dictionary reset
+ * or beyond the dictionary size, input or output that ends inside a symbol, payload left over); GC_ERR_DST_SMALL: dstCapacity below dst_off + dst_size of a unit. */
+typedef struct gc_lzma2_unit {
+    uint64_t src_off, src_size;      /* the unit's chunks inside the compressed buffer */
+    uint64_t dst_off, dst_size;      /* where its content goes, and how much it is */
+    uint32_t n_chunks;
+    uint32_t flags;                  /* bits 0-2: the largest lc + lp of any props byte in the unit; bit 8: the end marker follows this unit */
+} gc_lzma2_unit;
+int         gc_lzma2_scan_prefix(const void* src, size_t n, gc_lzma2_unit* units, size_t maxUnits, size_t* nUnits, uint64_t* contentTotal, size_t* consumed, int* ended);
+int         gc_lzma2_decompress_device(gc_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t dstCapacity, unsigned char dictProp,
+                                       const gc_lzma2_unit* units, size_t nUnits, size_t* decompressedSize);
+int         gc_lzma2_decompress_host(gc_ctx* ctx, const void* src, size_t n, void* dst, size_t dstCapacity, unsigned char dictProp, size_t* decompressedSize);
+/* HIP-event duration of the decode kernels of the last gc_lzma2_decompress_* call */
+int         gc_lzma2_decompress_timing(gc_ctx* ctx, float* ms);
+
 /* raw stream handle (hipStream_t) so callers can order their own work against the context */
 void*       gc_ctx_stream(gc_ctx* ctx);
 
