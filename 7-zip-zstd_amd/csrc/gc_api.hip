@@ -601,7 +601,7 @@ static int launch_finder_part(gc_ctx* c, const GcLzPlan& plan, hipStream_t st, u
     HIPCHK(c, hipEventRecord(ev[1], st));
     GC_LAUNCH(MFSEL(gc_mf_scan_kernel), g.nFrames, 1024, st, cnt, g.tilesPerFrame);
     HIPCHK(c, hipEventRecord(ev[2], st));
-    GC_LAUNCH(MFSEL(gc_mf_scatter_kernel), perT * GC_XCDS, nParts, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt, ent);
+    GC_LAUNCH(MFSEL(gc_mf_scatter_kernel), perT * GC_XCDS, g.scatterT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt, ent);
     HIPCHK(c, hipEventRecord(ev[3], st));
     MF_LINK(cnt, ent, ent2);
     HIPCHK(c, hipEventRecord(ev[4], st));
@@ -628,7 +628,7 @@ static int launch_finder_part(gc_ctx* c, const GcLzPlan& plan, hipStream_t st, u
     if (plan.farPass) {                                         // second pass with 16- / 12-byte keys, merged into rec (timed with W5)
         GC_LAUNCH(MFSEL(gc_mf_count_far_kernel), perT * GC_XCDS, nParts, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, cnt);
         GC_LAUNCH(MFSEL(gc_mf_scan_kernel), g.nFrames, 1024, st, cnt, g.tilesPerFrame);
-        GC_LAUNCH(MFSEL(gc_mf_scatter_far_kernel), perT * GC_XCDS, nParts, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt, ent);
+        GC_LAUNCH(MFSEL(gc_mf_scatter_far_kernel), perT * GC_XCDS, g.scatterT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt, ent);
         MF_LINK(cnt, ent, ent2);
         GC_LAUNCH(MFSEL(gc_mf_verify_far_kernel), perT * GC_XCDS, g.verifyT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt,
                   (const GcMfEntry*)ent2, rec);
@@ -636,7 +636,7 @@ static int launch_finder_part(gc_ctx* c, const GcLzPlan& plan, hipStream_t st, u
     if (plan.farPass2) {                                        // third pass of the far kind: keys of 32 / 24 bytes, capped records ranked by what lies behind the cap (gc_lz_window.hip MF_FAR2; timed with W5)
         GC_LAUNCH(MFSEL(gc_mf_count_far2_kernel), perT * GC_XCDS, nParts, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, cnt);
         GC_LAUNCH(MFSEL(gc_mf_scan_kernel), g.nFrames, 1024, st, cnt, g.tilesPerFrame);
-        GC_LAUNCH(MFSEL(gc_mf_scatter_far2_kernel), perT * GC_XCDS, nParts, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt, ent);
+        GC_LAUNCH(MFSEL(gc_mf_scatter_far2_kernel), perT * GC_XCDS, g.scatterT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt, ent);
         MF_LINK(cnt, ent, ent2);
         GC_LAUNCH(MFSEL(gc_mf_verify_far2_kernel), perT * GC_XCDS, g.verifyT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt,
                   (const GcMfEntry*)ent2, rec);
@@ -661,7 +661,7 @@ static int launch_finder_part(gc_ctx* c, const GcLzPlan& plan, hipStream_t st, u
         uint32_t* cntS = c->mfCnt;
         GC_LAUNCH(MFSEL(gc_mf_count_short_kernel), perTs * GC_XCDS, nParts, st, src, (uint64_t)n, fbS, gs.nTiles, perTs, cntS);
         GC_LAUNCH(MFSEL(gc_mf_scan_kernel), gs.nFrames, 1024, st, cntS, gs.tilesPerFrame);
-        GC_LAUNCH(MFSEL(gc_mf_scatter_short_kernel), perTs * GC_XCDS, nParts, st, src, (uint64_t)n, fbS, gs.nTiles, perTs, (const uint32_t*)cntS, ent);
+        GC_LAUNCH(MFSEL(gc_mf_scatter_short_kernel), perTs * GC_XCDS, gs.scatterT, st, src, (uint64_t)n, fbS, gs.nTiles, perTs, (const uint32_t*)cntS, ent);
         {   uint32_t* ticket_ = c->mfTicket + part * 16u + linkLaunch++;
             const uint32_t gridS = nListsS * GC_MF_LINK_SEGS < c->nCU * linkWpc ? nListsS * GC_MF_LINK_SEGS : c->nCU * linkWpc;
             GC_LAUNCH(MFSEL(gc_mf_link_kernel), gridS, 64, st, (const uint32_t*)cntS, (const GcMfEntry*)ent, ent2, gs.tilesPerFrame, gs.frameBytes, nListsS, ticket_); }

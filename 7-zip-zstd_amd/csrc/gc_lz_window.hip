@@ -36,9 +36,13 @@
 // everything below depends on the geometry: one namespace per geometry, so that the two copies of the helpers never meet at link time
 namespace MFK(gc_mf_ns) {
 
-#define MF_T         GC_MF_PARTS      // W1 / W3: threads per tile (one per partition)
-#define MF_WAVES     (MF_T / 64u)
-static_assert(MF_T == GC_MF_PARTS, "W1/W3 use one thread per partition for the histogram rows");
+#define MF_T         GC_MF_PARTS      // W1: threads per tile (one per partition)
+static_assert(MF_T == GC_MF_PARTS, "W1 uses one thread per partition for the histogram row");
+#define MF_PWAVES    (GC_MF_PARTS / 64u)                  // waves that hold one partition per lane
+#define MFS_T        GC_MF_SCATTER_T  // W3: threads per tile
+#define MFS_WAVES    (MFS_T / 64u)
+#define MFS_ROUNDS   (GC_MF_TILE / MFS_T)                 // rounds of 64 positions per wave
+static_assert(MFS_T >= GC_MF_PARTS && MFS_T % 64u == 0u && GC_MF_TILE % (2u * MFS_T) == 0u && GC_MF_PARTS < 0xFFFFu, "W3: the first GC_MF_PARTS threads do the offsets; whole rounds, two per register");
 #define MF_STAGE_PAD 16u              // bytes staged in front of / behind the tile
 #define MF_STAGE_WORDS ((GC_MF_TILE + 2u * MF_STAGE_PAD + 32u) / 4u)     // (+ 32: the keys of MF_FAR2 read 32 bytes from a position)
 
@@ -253,16 +257,29 @@ MFK(gc_mf_scan_kernel)(uint32_t* __restrict__ cnt, uint32_t tilesPerFrame)
 
 // ------------------------------------------------------------------------------------------------ W3 scatter
 // Stable counting sort of one tile by partition, staged through LDS as a permutation (16-bit tile positions), so that every
-// partition's run leaves the CU as one contiguous, coalesced store stream.  Wave w owns quarter w of the tile; ranks inside a
-// 64-position round come from ballots (position order = lane order), so the order inside a partition is position order.
+// partition's run leaves the CU as one contiguous, coalesced store stream.
+//
+// The workgroup has MFS_T threads, a number of its own (gc_mf.h GC_MF_SCATTER_T): only the offsets step works per partition, and
+// the first GC_MF_PARTS threads do it.  Wave w owns slice w of the tile (GC_MF_TILE / MFS_WAVES positions, MFS_ROUNDS rounds of 64)
+// in position order; the rank of a position inside its round comes from the returning LDS add (lanes that hit one counter are
+// served in lane order = position order), rounds follow each other in program order and the slices of a partition lie behind each
+// other in wave order -- so the order inside a partition's run is position order whatever MFS_T is.
+//
+// A position's keys are evaluated twice: in pass A, which keeps the partition (or "not listed") of each of the thread's MFS_ROUNDS
+// positions in registers, 16 bits each, for pass B to rank by; and in the output loop, which rebuilds the 8-byte entry from the
+// staged bytes (keeping the entries would take 8 bytes of LDS per position).  Pass B reads no input bytes and hashes nothing.
+//
+// Fast geometry: 512 threads per 8 KiB tile, 48 VGPRs, 33 872 B of LDS -> four workgroups = all 32 wave slots of a CU (with one thread per
+// partition, 256, it was 30 800 B: five workgroups, 20 waves).  The wide geometry keeps 1024 threads per 16 KiB tile.
+// zstd level 3 on 1 GB, one MI355X, both in one session: 3.13 -> 2.57 ms, the traffic (9.1 GB counted) is untouched (profiles/scatter_full_cu.md).
 template <int MODE>
 __device__ __forceinline__ void mf_scatter_body(const uint8_t* __restrict__ src, uint64_t srcSize, uint32_t frameBlocks, uint32_t nTiles, uint32_t per,
                      const uint32_t* __restrict__ offs, GcMfEntry* __restrict__ ent)
 {
     __shared__ uint32_t sW[MF_STAGE_WORDS];
-    __shared__ uint32_t sRun[MF_WAVES][GC_MF_PARTS];              // pass A: counts; pass B: next free slot of (wave, partition)
-    __shared__ uint32_t sLocal[GC_MF_PARTS], sGlob[GC_MF_PARTS];
-    __shared__ uint32_t sWaveTot[MF_WAVES];
+    __shared__ uint32_t sRun[MFS_WAVES][GC_MF_PARTS];             // pass A: counts; pass B: next free slot of (wave, partition)
+    __shared__ uint32_t sDelta[GC_MF_PARTS];                      // where the partition's run starts in HBM minus where it starts in the sorted tile
+    __shared__ uint32_t sWaveTot[MF_PWAVES];
     __shared__ uint16_t sPerm[GC_MF_TILE];
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
     const uint32_t tile = mf_item(blockIdx.x, per);
@@ -270,69 +287,74 @@ __device__ __forceinline__ void mf_scatter_body(const uint8_t* __restrict__ src,
     const MfTile T = mf_tile(tile, frameBlocks, srcSize);
     if (T.len == 0u) return;
     const uint32_t TPF = MF_F(frameBlocks) * GC_MF_TILES_PER_BLOCK;
-    for (uint32_t w = 0; w < MF_WAVES; w++) sRun[w][t] = 0;
-    mf_stage(sW, MF_STAGE_WORDS, src, srcSize, T.tileStart, t, MF_T);
+    for (uint32_t i = t; i < MFS_WAVES * GC_MF_PARTS; i += MFS_T) (&sRun[0][0])[i] = 0;
+    mf_stage(sW, MF_STAGE_WORDS, src, srcSize, T.tileStart, t, MFS_T);
     __syncthreads();
-    const uint32_t qBase = wave * (GC_MF_TILE / MF_WAVES);
-    // pass A: per-wave histograms
-    for (uint32_t r = 0; r < GC_MF_TILE / MF_T; r++) {                // (a wave owns GC_MF_TILE / MF_WAVES positions = GC_MF_TILE / MF_T rounds of 64)
+    const uint32_t qBase = wave * (GC_MF_TILE / MFS_WAVES);
+    // pass A: per-wave histograms; pk: partition of the position of round r, 0xFFFF = not listed (two rounds per register)
+    uint32_t pk[MFS_ROUNDS / 2u];
+#pragma unroll
+    for (uint32_t r = 0; r < MFS_ROUNDS; r++) {
         const MfKeys k = mf_keys<MODE>(sW, qBase + r * 64u + lane, T);
+        const uint32_t p = k.ok ? k.part : 0xFFFFu;
+        pk[r >> 1] = (r & 1u) ? (pk[r >> 1] | (p << 16)) : p;
         if (k.ok) atomicAdd(&sRun[wave][k.part], 1u);
     }
     __syncthreads();
     // offsets: thread t = partition t
-    uint32_t c[MF_WAVES], tot = 0;
-    for (uint32_t w = 0; w < MF_WAVES; w++) { c[w] = sRun[w][t]; tot += c[w]; }
-    const uint32_t incl = gc_wave_incl_sum(tot);
-    if (lane == 63u) sWaveTot[wave] = incl;
+    uint32_t tot = 0, incl = 0;
+    if (t < GC_MF_PARTS) {
+        for (uint32_t w = 0; w < MFS_WAVES; w++) tot += sRun[w][t];
+        incl = gc_wave_incl_sum(tot);
+        if (lane == 63u) sWaveTot[wave] = incl;
+    }
     __syncthreads();
-    {
+    if (t < GC_MF_PARTS) {
         uint32_t before = 0;
-        for (uint32_t w = 0; w < MF_WAVES; w++) if (w < wave) before += sWaveTot[w];
+        for (uint32_t w = 0; w < MF_PWAVES; w++) if (w < wave) before += sWaveTot[w];
         uint32_t ls = before + incl - tot;
-        sLocal[t] = ls;
-        for (uint32_t w = 0; w < MF_WAVES; w++) { sRun[w][t] = ls; ls += c[w]; }
-        sGlob[t] = offs[((uint64_t)T.frame * (TPF + 1u) + T.tif) * GC_MF_PARTS + t];
+        sDelta[t] = offs[((uint64_t)T.frame * (TPF + 1u) + T.tif) * GC_MF_PARTS + t] - ls;
+        for (uint32_t w = 0; w < MFS_WAVES; w++) { const uint32_t c = sRun[w][t]; sRun[w][t] = ls; ls += c; }
     }
     __syncthreads();
     uint32_t nEnt = 0;
-    for (uint32_t w = 0; w < MF_WAVES; w++) nEnt += sWaveTot[w];
+    for (uint32_t w = 0; w < MF_PWAVES; w++) nEnt += sWaveTot[w];
     // pass B: stable ranks -> permutation
-    for (uint32_t r = 0; r < GC_MF_TILE / MF_T; r++) {
-        const uint32_t q = qBase + r * 64u + lane;
-        const MfKeys k = mf_keys<MODE>(sW, q, T);
+#pragma unroll
+    for (uint32_t r = 0; r < MFS_ROUNDS; r++) {
+        const uint32_t p = (pk[r >> 1] >> ((r & 1u) * 16u)) & 0xFFFFu;
         // one returning ds_add per position: the LDS unit serves the lanes that hit one counter in lane order (the property W4's ds_max
         // relies on), lanes are positions, rounds follow each other in program order -- so the value returned is the position's stable rank
-        if (k.ok) sPerm[atomicAdd(&sRun[wave][k.part], 1u)] = (uint16_t)q;
+        if (p != 0xFFFFu) sPerm[atomicAdd(&sRun[wave][p], 1u)] = (uint16_t)(qBase + r * 64u + lane);
         gc_wave_step();
     }
     __syncthreads();
     // output: slot j of the sorted tile -> its partition's run in HBM
     GcMfEntry* E = ent + (uint64_t)T.frame * ((uint64_t)MF_F(frameBlocks) * GC_ZSTD_BLOCK_MAX);
-    for (uint32_t j = t; j < nEnt; j += MF_T) {
+    for (uint32_t j = t; j < nEnt; j += MFS_T) {
         const MfKeys k = mf_keys<MODE>(sW, sPerm[j], T);
-        E[sGlob[k.part] + (j - sLocal[k.part])] = k.entry;
+        E[sDelta[k.part] + j] = k.entry;
     }
 }
-extern "C" __global__ void __launch_bounds__(MF_T)
+extern "C" __global__ void __launch_bounds__(MFS_T)
 MFK(gc_mf_scatter_kernel)(const uint8_t* __restrict__ src, uint64_t srcSize, uint32_t frameBlocks, uint32_t nTiles, uint32_t per,
                      const uint32_t* __restrict__ offs, GcMfEntry* __restrict__ ent)
 {
     mf_scatter_body<MF_BASE>(src, srcSize, frameBlocks, nTiles, per, offs, ent);
 }
-extern "C" __global__ void __launch_bounds__(MF_T)
+extern "C" __global__ void __launch_bounds__(MFS_T)
 MFK(gc_mf_scatter_short_kernel)(const uint8_t* __restrict__ src, uint64_t srcSize, uint32_t frameBlocks, uint32_t nTiles, uint32_t per,
                            const uint32_t* __restrict__ offs, GcMfEntry* __restrict__ ent)
 {
     mf_scatter_body<MF_SHORT>(src, srcSize, frameBlocks, nTiles, per, offs, ent);
 }
-extern "C" __global__ void __launch_bounds__(MF_T)
+extern "C" __global__ void __launch_bounds__(MFS_T)
 MFK(gc_mf_scatter_far_kernel)(const uint8_t* __restrict__ src, uint64_t srcSize, uint32_t frameBlocks, uint32_t nTiles, uint32_t per,
                          const uint32_t* __restrict__ offs, GcMfEntry* __restrict__ ent)
 {
     mf_scatter_body<MF_FAR>(src, srcSize, frameBlocks, nTiles, per, offs, ent);
 }
-extern "C" __global__ void __launch_bounds__(MF_T)
+extern "C" __global__ void __launch_bounds__(MFS_T)
 MFK(gc_mf_scatter_far2_kernel)(const uint8_t* __restrict__ src, uint64_t srcSize, uint32_t frameBlocks, uint32_t nTiles, uint32_t per,
                          const uint32_t* __restrict__ offs, GcMfEntry* __restrict__ ent)
 {

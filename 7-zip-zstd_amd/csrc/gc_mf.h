@@ -40,6 +40,8 @@
 #define GC_MF_FAST_TILE_LOG 13u
 #define GC_MF_FAST_PART_LOG 8u
 #define GC_MF_FAST_VERIFY_T 512u
+#define GC_MF_WIDE_SCATTER_T 1024u                        // W3: threads per tile (>= the partitions; gc_lz_window.hip mf_scatter_body)
+#define GC_MF_FAST_SCATTER_T 512u                         //     eight waves per 8 KiB tile: four workgroups fill a CU's 32 wave slots
 #ifdef GC_MF_FAST
 #define GC_MF_TILE_LOG    GC_MF_FAST_TILE_LOG
 #define GC_MF_PART_LOG    GC_MF_FAST_PART_LOG
@@ -79,7 +81,9 @@ typedef uint64_t GcMfEntry;
 #define GC_MF_PARSE_T     1024u                           // W6: threads per block
 #ifdef GC_MF_FAST
 #define GC_MF_VERIFY_T    GC_MF_FAST_VERIFY_T
+#define GC_MF_SCATTER_T   GC_MF_FAST_SCATTER_T
 #else
+#define GC_MF_SCATTER_T   GC_MF_WIDE_SCATTER_T
 #define GC_MF_VERIFY_T    GC_MF_WIDE_VERIFY_T             // W5: threads per tile (>= GC_MF_PARTS: one thread per run start)
 #endif
 #define GC_MF_LINK_SEGS   8u                              // W4: waves per (frame, partition): long lists are linked in segments
@@ -100,7 +104,7 @@ typedef uint64_t GcMfEntry;
 
 // W5 -> W6: one 32-bit match record per input position, (offset << 8) | length; 0 = no match
 struct GcMfGeom {
-    uint32_t tileLog, partLog, verifyT;    // which geometry (wide / fast)
+    uint32_t tileLog, partLog, verifyT, scatterT;    // which geometry (wide / fast)
     uint32_t frameBlocks;     // F
     uint32_t nBlocks;
     uint32_t nFrames;
@@ -115,7 +119,7 @@ static inline GcMfGeom gc_mf_geom(uint64_t n, uint32_t frameArg, bool fast)
     GcMfGeom g;
     const uint32_t frameBlocks = MF_F(frameArg);
     g.tileLog = fast ? GC_MF_FAST_TILE_LOG : GC_MF_WIDE_TILE_LOG; g.partLog = fast ? GC_MF_FAST_PART_LOG : GC_MF_WIDE_PART_LOG;
-    g.verifyT = fast ? GC_MF_FAST_VERIFY_T : GC_MF_WIDE_VERIFY_T;
+    g.verifyT = fast ? GC_MF_FAST_VERIFY_T : GC_MF_WIDE_VERIFY_T; g.scatterT = fast ? GC_MF_FAST_SCATTER_T : GC_MF_WIDE_SCATTER_T;
     g.frameBlocks = frameBlocks;
     g.nBlocks = gc_num_blocks(n);
     g.nFrames = ((g.nBlocks + MF_C(frameArg) - 1u) / MF_C(frameArg)) * MF_FPG(frameArg);      // (no overlap: C = F, one frame per group)
