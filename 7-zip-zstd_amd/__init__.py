@@ -28,7 +28,7 @@ EXPORTS = ["gc_test_hooks_enabled", "gc_lzfind_get_matches_device", "gc_device_c
            "gc_flzma2_compress_bound", "gc_flzma2_dict_prop", "gc_flzma2_compress_device", "gc_flzma2_finish", "gc_flzma2_compress_host",
            "gc_flzma2_last_timing",
            "gc_brotli_compress_bound", "gc_brotli_compress_device", "gc_brotli_finish", "gc_brotli_compress_host", "gc_brotli_last_timing",
-           "gc_ctx_set_option", "gc_crc32_device", "gc_codec_grain", "gc_codec_compress_bound", "gc_host_begin", "gc_host_size", "gc_host_fetch", "gc_codec_compress_host",
+           "gc_ctx_set_option", "gc_crc32_device", "gc_xxh64_device", "gc_zstd_checksum_timing", "gc_codec_grain", "gc_codec_compress_bound", "gc_host_begin", "gc_host_size", "gc_host_fetch", "gc_codec_compress_host",
            "gc_host_alloc", "gc_host_free", "gc_multi_create", "gc_multi_destroy", "gc_multi_workers", "gc_multi_last_error",
            "gc_multi_piece_bytes", "gc_multi_compress_host",
            "gc_bra_convert_device", "gc_bra_x86_convert_device", "gc_delta_convert_device", "gc_zstd_scan_frames", "gc_zstd_scan_prefix", "gc_zstd_decompress_device", "gc_zstd_decompress_host", "gc_zstd_decompress_timing", "gc_zstd_decompress_kernel_timing", "gc_zstd_decompress_wide_rounds", "gc_zstd_decompress_selfcheck", "gc_filter_host",
@@ -105,6 +105,10 @@ def load_library(path=None):
     lib.gc_ctx_stream.restype = C.c_void_p
     lib.gc_crc32_device.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     lib.gc_crc32_device.restype = C.c_int
+    lib.gc_xxh64_device.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.gc_xxh64_device.restype = C.c_int
+    lib.gc_zstd_checksum_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    lib.gc_zstd_checksum_timing.restype = C.c_int
     lib.gc_ctx_set_option.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.gc_ctx_set_option.restype = C.c_int
     lib.gc_codec_grain.argtypes = [C.c_int, C.c_int]
@@ -227,6 +231,15 @@ def crc32_device(ptr, n, lib_path=None):
     return v.value
 
 
+def xxh64_device(ptr, n, seed=0, lib_path=None):
+    """XXH64 (C/zstd/xxhash.h) of n bytes at a device pointer (under the emulator: any host pointer), any alignment."""
+    v = C.c_uint64(0)
+    rc = load_library(lib_path).gc_xxh64_device(ptr, n, seed & 0xFFFFFFFFFFFFFFFF, C.byref(v))
+    if rc != GC_OK:
+        raise GpuCodecError("gc_xxh64_device failed: %s" % _ERR.get(rc, rc))
+    return v.value
+
+
 def lzfind_get_matches_device(src_ptr, n, counts_ptr, pairs_ptr, stride, history=1 << 20, bt=False, cut=32, nice=64, lib_path=None):
     """IMatchFinder2::GetMatches of the reference's HC4 (bt=False) / BT4 (bt=True) for every position of n bytes at a device pointer (under the
     emulator: host pointers): counts[i] uint32 values at pairs[i * stride ...] (length, distance - 1, ...).  (C/LzFind.c:1362, :1219)"""
@@ -327,7 +340,7 @@ class _EncoderBase:
     def set_level(self, level):          # SetCoderProperties(kLevel)
         self.level = int(level)
 
-    OPT_ZSTD_SEEK_TABLE, OPT_BROTLI_PLAIN = 1, 2
+    OPT_ZSTD_SEEK_TABLE, OPT_BROTLI_PLAIN, OPT_ZSTD_CHECKSUM = 1, 2, 3
 
     def set_option(self, option, value=1):
         self._check(self._lib.gc_ctx_set_option(self._ctx, int(option), int(value)), "gc_ctx_set_option")
@@ -660,6 +673,15 @@ class ZstdEncoder(_EncoderBase):
         ms = (C.c_float * 6)()
         self._check(self._lib.gc_zstd_last_timing(self._ctx, ms), "gc_zstd_last_timing")
         return dict(zip(self.KERNELS, [float(x) for x in ms]))
+
+    CHECKSUM = 8                      # GC_ZSTD_CHECKSUM: per-call flag of code_pre / MultiEncoder.code
+
+    def checksum_ms(self):
+        """HIP-event duration of the content-checksum kernel in the last call (GC_OPT_ZSTD_CHECKSUM), or None if that call ran none."""
+        ms = C.c_float(0)
+        if self._lib.gc_zstd_checksum_timing(self._ctx, C.byref(ms)) != GC_OK:
+            return None
+        return float(ms.value)
 
     PHASES = ("lz.probe", "lz.insert", "lz.verify", "lz.double", "lz.chain", "lz.walk", "lz.emit",
               "seq.merge", "seq.codes", "seq.tables", "seq.chains", "seq.pack",

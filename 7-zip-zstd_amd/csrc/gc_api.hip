@@ -41,9 +41,10 @@ extern "C" __global__ void gc_zstd_seq_codes_kernel(const GcSeqRaw*, const GcBlo
 extern "C" __global__ void gc_zstd_seq_tables_kernel(const GcSeqHist*, const GcSectionInfo*, GcSeqTabG*, unsigned long long*);
 extern "C" __global__ void gc_zstd_seq_chain_kernel(const uint8_t*, const GcSectionInfo*, GcSeqTabG*, uint16_t*, unsigned long long*);
 extern "C" __global__ void gc_zstd_seq_pack_kernel(const uint64_t*, const uint8_t*, const uint16_t*, const GcSeqTabG*, uint8_t*, GcSectionInfo*, uint64_t, unsigned long long*);
-extern "C" __global__ void gc_zstd_plan_kernel(const GcSectionInfo*, uint32_t, uint64_t, uint64_t, uint32_t, GcFramePlan*, uint64_t*, uint32_t);
+extern "C" __global__ void gc_zstd_plan_kernel(const GcSectionInfo*, uint32_t, uint64_t, uint64_t, uint32_t, GcFramePlan*, uint64_t*, uint32_t, uint32_t);
 extern "C" __global__ void gc_zstd_emit_kernel(const uint8_t*, uint64_t, const uint8_t*, const uint8_t*, const GcSectionInfo*,
-                                               const GcFramePlan*, const uint64_t*, uint32_t, uint32_t, uint8_t*);
+                                               const GcFramePlan*, const uint64_t*, uint32_t, uint32_t, uint8_t*, const uint64_t*);
+extern "C" __global__ void gc_zstd_xxh64_kernel(const uint8_t*, uint64_t, uint64_t, uint32_t, uint64_t, uint64_t*);      // K0x (gc_xxh64.h)
 
 extern "C" __global__ void gc_mf_count_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t*);
 extern "C" __global__ void gc_mf_scan_kernel(uint32_t*, uint32_t);
@@ -112,7 +113,12 @@ struct gc_ctx {
     hipStream_t stream3;      // FLZMA2: range-coder stage
     hipEvent_t evPart[GC_MAX_PARTS][GC_PART_EVENTS];   // per input part: stage boundaries (see gc_flzma2_compress_device)
     uint32_t nParts;
-    uint32_t optSeekTable, optBrotliPlain;   // gc_ctx_set_option
+    uint32_t optSeekTable, optBrotliPlain, optChecksum;   // gc_ctx_set_option
+    // zstd content checksums (GC_OPT_ZSTD_CHECKSUM): K0x reads nothing but the input and runs beside the whole pipeline.  It has a stream of its own (created with
+    // the first call that wants checksums): stream2 / stream3 carry K3 / K2 in order, which would queue behind a hash that outlasts the finder in a small call.
+    hipStream_t streamHash; hipEvent_t evHash[2];      // K0x start, end
+    uint64_t* xxh; size_t xxhCap;                      // XXH64 per frame
+    bool hashTimed;                                    // the last compress call ran K0x (evHash brackets it)
     uint32_t dbgFrameBlocks, dbgPartFrames;   // test hooks (env GC_FRAME_BLOCKS / GC_PART_FRAMES): small frames / parts so that
                                               // the multi-frame and multi-part paths can be exercised on small inputs
     hipEvent_t ev[8];         // 0 lz start, 1 lz end, 2 huf end, 3 seq start, 4 seq end, 5 plan start, 6 plan end, 7 emit end
@@ -186,7 +192,8 @@ extern "C" int gc_device_count(void)
 extern "C" size_t gc_zstd_compress_bound(size_t n)
 {
     size_t nb = n ? (n + GC_ZSTD_BLOCK_MAX - 1) / GC_ZSTD_BLOCK_MAX : 1;
-    return n + nb * GC_FRAME_OVERHEAD + 16 + nb * 8 + 17;       // (+ the optional seek table: 8 bytes per frame, 17 of header and footer)
+    return n + nb * GC_FRAME_OVERHEAD + 16 + nb * 8 + 17        // (+ the optional seek table: 8 bytes per frame, 17 of header and footer)
+         + nb * 8;                                              // (+ the optional content checksums: 4 bytes behind every frame and 4 more per seek-table entry, every block a frame of its own at worst)
 }
 
 static void free_workspace(gc_ctx* c);
@@ -248,6 +255,8 @@ static void ctx_release(gc_ctx* c)
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     free_workspace(c);
+    if (c->streamHash) hipStreamSynchronize(c->streamHash);
+    hipFree(c->xxh);
     hipFree(c->prof); hipFree(c->mfTicket); hipFree(c->result); if (c->hostResult) hipHostFree(c->hostResult); hipFree(c->dIn); hipFree(c->dOut); hipFree(c->dPre);
     gc_brd_release(&c->brd);
     gc_l2d_release(&c->l2d);
@@ -260,6 +269,8 @@ static void ctx_release(gc_ctx* c)
         if (c->evShort[p]) hipEventDestroy(c->evShort[p]);
         for (uint32_t i = 0; i < GC_PART_EVENTS; i++) if (c->evPart[p][i]) hipEventDestroy(c->evPart[p][i]);
     }
+    for (int i = 0; i < 2; i++) if (c->evHash[i]) hipEventDestroy(c->evHash[i]);
+    if (c->streamHash) hipStreamDestroy(c->streamHash);
     if (c->stream3) hipStreamDestroy(c->stream3);
     if (c->stream2) hipStreamDestroy(c->stream2);
     if (c->stream) hipStreamDestroy(c->stream);
@@ -276,6 +287,7 @@ extern "C" int gc_ctx_set_option(gc_ctx* c, int option, int value)
 {
     if (!c) return GC_ERR_PARAM;
     if (option == GC_OPT_ZSTD_SEEK_TABLE) c->optSeekTable = value != 0;
+    else if (option == GC_OPT_ZSTD_CHECKSUM) c->optChecksum = value != 0;
     else if (option == GC_OPT_BROTLI_PLAIN) c->optBrotliPlain = value ? ((uint32_t)value & 7u) | 1u : 0u;     // bit 0 plain, bits 1 / 2: GC_BROTLI_NOT_FIRST / GC_BROTLI_NOT_LAST
     else return GC_ERR_PARAM;
     return GC_OK;
@@ -787,9 +799,16 @@ extern "C" int gc_zstd_compress_device(gc_ctx* c, const void* d_src, size_t n, v
     if (n == 0) {
         // empty input: one frame with FCS=0 and an empty raw last block (ZSTD_compress on 0 bytes does the same)
         static const uint8_t empty[9] = { 0x28, 0xB5, 0x2F, 0xFD, 0x20, 0x00, 0x01, 0x00, 0x00 };
-        if (dstCap < sizeof(empty)) return GC_ERR_DST_SMALL;
-        HIPCHK(c, hipMemcpyAsync(d_dst, empty, sizeof(empty), hipMemcpyHostToDevice, c->stream));
-        c->hostResult[0] = sizeof(empty); c->hostResult[1] = 0;
+        // ... with content checksums: Content_Checksum_Flag and XXH64("") = 0xEF46DB3751D8E999 behind the block; with a seek table as well, its one entry { 13, 0, checksum }
+        // (an empty input has never carried a seek table without checksums and keeps doing so)
+        static const uint8_t emptySum[13 + 29] = { 0x28, 0xB5, 0x2F, 0xFD, 0x24, 0x00, 0x01, 0x00, 0x00, 0x99, 0xE9, 0xD8, 0x51,
+                                                   0x5E, 0x2A, 0x4D, 0x18, 21, 0, 0, 0,  13, 0, 0, 0,  0, 0, 0, 0,  0x99, 0xE9, 0xD8, 0x51,  1, 0, 0, 0,  0x80,  0xB1, 0xEA, 0x92, 0x8F };
+        const uint8_t* const bytes = c->optChecksum ? emptySum : empty;
+        const size_t size = c->optChecksum ? (c->optSeekTable ? sizeof(emptySum) : 13u) : sizeof(empty);
+        c->hashTimed = false;
+        if (dstCap < size) return GC_ERR_DST_SMALL;
+        HIPCHK(c, hipMemcpyAsync(d_dst, bytes, size, hipMemcpyHostToDevice, c->stream));
+        c->hostResult[0] = size; c->hostResult[1] = 0;
         HIPCHK(c, hipMemcpyAsync(c->result, c->hostResult, 16, hipMemcpyHostToDevice, c->stream));
         c->pending = true;
         return GC_OK;
@@ -803,6 +822,25 @@ extern "C" int gc_zstd_compress_device(gc_ctx* c, const void* d_src, size_t n, v
     const uint32_t zArg = lz_frame_arg(GC_CODEC_ZSTD, level, nBlocks, c->dbgFrameBlocks);      // what the finder takes: overlapping frames from level 16, whose groups are the zstd frames
     const uint32_t zFrameBlocks = MF_C(zArg);                                                  // blocks per zstd frame
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+    c->hashTimed = false;
+    if (c->optChecksum) {       // K0x: XXH64 of every zstd frame's content, beside everything up to K4 (the input is ready where the main stream stands now)
+        const uint32_t hFrames = (nBlocks + zFrameBlocks - 1u) / zFrameBlocks;
+        if (!c->streamHash) {
+            if (hipStreamCreate(&c->streamHash) != hipSuccess) { c->streamHash = nullptr; snprintf(c->err, sizeof(c->err), "no stream for the content checksums"); return GC_ERR_HIP; }
+            for (int i = 0; i < 2; i++) if (!c->evHash[i]) HIPCHK(c, hipEventCreate(&c->evHash[i]));
+        }
+        if (hFrames > c->xxhCap) {
+            HIPCHK(c, hipStreamSynchronize(c->streamHash));
+            hipFree(c->xxh); c->xxh = nullptr; c->xxhCap = 0;
+            if (hipMalloc((void**)&c->xxh, (size_t)hFrames * sizeof(uint64_t)) != hipSuccess) { c->xxh = nullptr; snprintf(c->err, sizeof(c->err), "workspace allocation for %u frame checksums failed", hFrames); return GC_ERR_NOMEM; }
+            c->xxhCap = hFrames;
+        }
+        HIPCHK(c, hipStreamWaitEvent(c->streamHash, c->ev[0], 0));
+        HIPCHK(c, hipEventRecord(c->evHash[0], c->streamHash));
+        GC_LAUNCH(gc_zstd_xxh64_kernel, hFrames, GC_XXH64_T, c->streamHash, src, (uint64_t)n, (uint64_t)zFrameBlocks * GC_ZSTD_BLOCK_MAX, hFrames, (uint64_t)0, c->xxh);
+        HIPCHK(c, hipEventRecord(c->evHash[1], c->streamHash));
+        c->hashTimed = true;
+    }
     // The input can be taken in frame-aligned PARTS, the finder of part p + 1 (main stream) beside the entropy stage of part p (sequences on
     // stream2, literals on stream3).  Measured on MI355X (run r3_g, 1 GB of text at level 3): 1 part 30.9 ms, 2 parts 32.2, 4 parts 32.0,
     // 8 parts 35.2; 100 MB: 3.9 / 5.0 / 7.1 ms -- kernels that run beside each other take the CUs' LDS and wave slots from one another and
@@ -853,11 +891,13 @@ extern "C" int gc_zstd_compress_device(gc_ctx* c, const void* d_src, size_t n, v
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream3));
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev[2], 0));
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev[4], 0));
+    if (c->hashTimed) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evHash[1], 0));                // K0x joins in front of K4 / K5
     HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
-    GC_LAUNCH(gc_zstd_plan_kernel, 1, 1024, c->stream, (const GcSectionInfo*)c->info, nBlocks, (uint64_t)n, (uint64_t)dstCap, zFrameBlocks, c->plan, c->result, c->optSeekTable);
+    GC_LAUNCH(gc_zstd_plan_kernel, 1, 1024, c->stream, (const GcSectionInfo*)c->info, nBlocks, (uint64_t)n, (uint64_t)dstCap, zFrameBlocks, c->plan, c->result, c->optSeekTable, c->optChecksum);
     HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
     GC_LAUNCH(gc_zstd_emit_kernel, nBlocks + (c->optSeekTable ? 1u : 0u), 256, c->stream, src, (uint64_t)n, (const uint8_t*)c->litSec, (const uint8_t*)c->seqSec,
-              (const GcSectionInfo*)c->info, (const GcFramePlan*)c->plan, (const uint64_t*)c->result, nBlocks, zFrameBlocks, (uint8_t*)d_dst);
+              (const GcSectionInfo*)c->info, (const GcFramePlan*)c->plan, (const uint64_t*)c->result, nBlocks, zFrameBlocks, (uint8_t*)d_dst,
+              (const uint64_t*)(c->optChecksum ? c->xxh : nullptr));
     HIPCHK(c, hipEventRecord(c->ev[7], c->stream));
     HIPCHK(c, hipGetLastError());
     c->pending = true; c->timed = true; c->lastCodec = 0;
@@ -913,6 +953,29 @@ extern "C" int gc_zstd_last_timing(gc_ctx* c, float ms[6])
     HIPCHK(c, hipEventElapsedTime(&ms[3], c->ev[5], c->ev[6]));     // plan
     HIPCHK(c, hipEventElapsedTime(&ms[4], c->ev[6], c->ev[7]));     // emit
     HIPCHK(c, hipEventElapsedTime(&ms[5], c->ev[0], c->ev[7]));     // first kernel start -> last kernel end
+    return GC_OK;
+}
+
+// HIP-event duration of K0x (the content-checksum kernel) in the last gc_zstd_compress_device call; GC_ERR_PARAM if that call ran none
+extern "C" int gc_zstd_checksum_timing(gc_ctx* c, float* ms)
+{
+    if (!c || !ms || !c->timed || c->pending || c->lastCodec != 0 || !c->hashTimed) return GC_ERR_PARAM;
+    HIPCHK(c, hipEventElapsedTime(ms, c->evHash[0], c->evHash[1]));
+    return GC_OK;
+}
+
+// XXH64 of n bytes in device memory: K0x over ONE frame of n bytes, with a seed; on the calling thread's stream (gc_host_stream.h), synchronous like gc_crc32_device
+extern "C" int gc_xxh64_device(const void* d_src, size_t n, uint64_t seed, uint64_t* hash)
+{
+    if ((!d_src && n) || !hash) return GC_ERR_PARAM;
+    uint64_t* dOut = nullptr;
+    if (gc_scratch_alloc((void**)&dOut, sizeof(uint64_t)) != hipSuccess) return GC_ERR_NOMEM;
+    GC_LAUNCH(gc_zstd_xxh64_kernel, 1, GC_XXH64_T, gc_tls_stream, (const uint8_t*)d_src, (uint64_t)n, (uint64_t)n, 1u, seed, dOut);
+    uint64_t h = 0;
+    const bool ok = gc_copy_sync(&h, dOut, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess;
+    gc_scratch_free(dOut);
+    if (!ok) return GC_ERR_HIP;
+    *hash = h;
     return GC_OK;
 }
 
@@ -1220,6 +1283,13 @@ extern "C" int gc_host_begin_pre(gc_ctx* c, int codec, const void* src, size_t n
         c->optBrotliPlain = (flags & 7u) | 1u;
         const int rc = gc_brotli_compress_device(c, d_in, n, c->dOut, c->dOutCap, level);
         c->optBrotliPlain = keep;
+        return rc;
+    }
+    if (codec == GC_CODEC_ZSTD && (flags & GC_ZSTD_CHECKSUM)) {       // per-call form of GC_OPT_ZSTD_CHECKSUM, likewise
+        const uint32_t keep = c->optChecksum;
+        c->optChecksum = 1u;
+        const int rc = gc_zstd_compress_device(c, d_in, n, c->dOut, c->dOutCap, level);
+        c->optChecksum = keep;
         return rc;
     }
     return codec == GC_CODEC_ZSTD ? gc_zstd_compress_device(c, d_in, n, c->dOut, c->dOutCap, level)

@@ -47,6 +47,10 @@ struct GcSectionInfo {
 // worst-case frame: 4 magic + 1 FHD + 4 FCS + 3 block header + payload
 #define GC_FRAME_OVERHEAD 12u
 
+// K0x (gc_xxh64.hip): bytes of a frame's content staged per step of the content-checksum kernel
+#define GC_XXH64_TILE 8192u
+#define GC_XXH64_T    320u  // its threads per block: one wave on the chain, four staging
+
 #define GC_SEQ_T      256u  // K3a / K3d: threads per block
 #define GC_LZ_PHASES  7   // K1 phase profile slots: probe, insert, verify, double, chain, walk, emit
 #define GC_SEQ_PHASES 9   // K3 phase profile slots: merge, codes, tables, chains, pack + chain sub-phases: stage, warm-up, walk, copy-out

@@ -7,8 +7,13 @@
 // every block is its own frame.  The reference decoder accepts any number of concatenated frames
 // (CPP/7zip/Compress/ZstdDecoder.cpp:145-158), which is what makes frames independent units for the GPU and, one level
 // up, for range-splitting across GPUs.
+//
+// Content checksums (gc_ctx_set_option GC_OPT_ZSTD_CHECKSUM; what ZSTD_c_checksumFlag = 1 writes, ZSTD_writeEpilogue zstd_compress.c:5225-5232): K0x
+// (gc_xxh64.hip) has left XXH64 of every frame's content in `hash`; K4 counts 4 more bytes behind the last block of every frame, K5 sets
+// Content_Checksum_Flag in the frame header descriptor and the workgroup of that block writes the low 32 bits there, little endian.
 #include "gc_common.h"
 #include "gc_device.h"
+#include "gc_xxh64.h"      // K0x: gc_zstd_xxh64_kernel
 
 #define FRAME_T 256u
 
@@ -27,7 +32,8 @@ __device__ __forceinline__ uint32_t frame_len_of(uint32_t b, uint32_t frameBlock
 extern "C" __global__ void __launch_bounds__(1024)
 gc_zstd_plan_kernel(const GcSectionInfo* __restrict__ info, uint32_t nBlocks, uint64_t srcSize, uint64_t dstCap, uint32_t frameBlocks,
                     GcFramePlan* __restrict__ plan, uint64_t* __restrict__ result /* [0]=total bytes, [1]=error */,
-                    uint32_t seekTable /* 1: a seek table (skippable frame) follows the last frame */)
+                    uint32_t seekTable /* 1: a seek table (skippable frame) follows the last frame */,
+                    uint32_t checksum /* 1: every frame ends with its content checksum, and the seek table lists them */)
 {
     __shared__ uint32_t sWave[16];
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
@@ -42,7 +48,8 @@ gc_zstd_plan_kernel(const GcSectionInfo* __restrict__ info, uint32_t nBlocks, ui
             const uint64_t payload = (uint64_t)si.litSecSize + si.seqSecSize;
             comp = (si.seqSecSize != 0xFFFFFFFFu && payload < blockLen) ? 1u : 0u;
             const uint32_t hdr = (b % frameBlocks) == 0u ? frame_hdr_size(frame_len_of(b, frameBlocks, srcSize)) : 0u;
-            size = hdr + 3u + (comp ? (uint32_t)payload : blockLen);
+            const bool last = (b % frameBlocks) == frameBlocks - 1u || b == nBlocks - 1u;
+            size = hdr + 3u + (comp ? (uint32_t)payload : blockLen) + ((checksum && last) ? 4u : 0u);
         }
         uint32_t incl = gc_wave_incl_sum(size);
         if (lane == 63u) sWave[wave] = incl;
@@ -55,35 +62,39 @@ gc_zstd_plan_kernel(const GcSectionInfo* __restrict__ info, uint32_t nBlocks, ui
     }
     if (t == 0) {
         const uint32_t nFrames = (nBlocks + frameBlocks - 1u) / frameBlocks;
-        const uint64_t total = carry + (seekTable ? 8ull + 8ull * nFrames + 9ull : 0ull);
+        const uint64_t total = carry + (seekTable ? 8ull + (checksum ? 12ull : 8ull) * nFrames + 9ull : 0ull);
         result[0] = total; result[1] = total > dstCap ? 1u : 0u;
     }
 }
 
 // K5: one workgroup per block writes its frame; with a seek table one more workgroup (blockIdx == nBlocks) writes it:
-//   0x184D2A5E | size of the rest | per frame { compressed size, decompressed size } | number of frames | descriptor 0 | 0x8F92EAB1
-// (zstd seekable format, contrib/seekable_format/zstd_seekable_compression_format.md; little endian, no per-frame checksums)
+//   0x184D2A5E | size of the rest | per frame { compressed size, decompressed size [, checksum] } | number of frames | descriptor | 0x8F92EAB1
+// (zstd seekable format, contrib/seekable_format/zstd_seekable_compression_format.md; little endian.  Descriptor 0: entries of 8 bytes, no per-frame
+// checksums; with content checksums (`hash` != null) descriptor 0x80 = Checksum_Flag and entries of 12 bytes, the third word the low 32 bits of XXH64 of
+// the frame's content -- the value the frame itself ends with)
 extern "C" __global__ void __launch_bounds__(FRAME_T)
 gc_zstd_emit_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, const uint8_t* __restrict__ litSec,
                     const uint8_t* __restrict__ seqSec, const GcSectionInfo* __restrict__ info,
                     const GcFramePlan* __restrict__ plan, const uint64_t* __restrict__ result, uint32_t nBlocks, uint32_t frameBlocks,
-                    uint8_t* __restrict__ dst)
+                    uint8_t* __restrict__ dst, const uint64_t* __restrict__ hash /* per frame, or null: no content checksums */)
 {
     if (result[1]) return;                       // output buffer too small: write nothing
     const uint32_t t = threadIdx.x, b = blockIdx.x;
     if (b == nBlocks) {                          // the seek table (only launched when one is wanted)
         const uint32_t nFrames = (nBlocks + frameBlocks - 1u) / frameBlocks;
-        const uint64_t tableBytes = 8ull + 8ull * nFrames + 9ull, framesEnd = result[0] - tableBytes;
+        const uint64_t entry = hash ? 12ull : 8ull;
+        const uint64_t tableBytes = 8ull + entry * nFrames + 9ull, framesEnd = result[0] - tableBytes;
         uint8_t* o = dst + framesEnd;
         auto put32 = [](uint8_t* q, uint32_t v) { q[0] = (uint8_t)v; q[1] = (uint8_t)(v >> 8); q[2] = (uint8_t)(v >> 16); q[3] = (uint8_t)(v >> 24); };
         if (t == 0) { put32(o, 0x184D2A5Eu); put32(o + 4, (uint32_t)(tableBytes - 8ull)); }
         for (uint32_t f = t; f < nFrames; f += FRAME_T) {
             const uint32_t b0 = f * frameBlocks, b1 = b0 + frameBlocks;
             const uint64_t end = b1 < nBlocks ? plan[b1].off : framesEnd;
-            put32(o + 8u + 8ull * f, (uint32_t)(end - plan[b0].off));
-            put32(o + 12u + 8ull * f, frame_len_of(b0, frameBlocks, srcSize));
+            put32(o + 8u + entry * f, (uint32_t)(end - plan[b0].off));
+            put32(o + 12u + entry * f, frame_len_of(b0, frameBlocks, srcSize));
+            if (hash) put32(o + 16u + entry * f, (uint32_t)hash[f]);
         }
-        if (t == 0) { uint8_t* ft = o + 8u + 8ull * nFrames; put32(ft, nFrames); ft[4] = 0; put32(ft + 5, 0x8F92EAB1u); }
+        if (t == 0) { uint8_t* ft = o + 8u + entry * nFrames; put32(ft, nFrames); ft[4] = hash ? 0x80 : 0; put32(ft + 5, 0x8F92EAB1u); }
         return;
     }
     const uint64_t base = (uint64_t)b * GC_ZSTD_BLOCK_MAX;
@@ -98,7 +109,7 @@ gc_zstd_emit_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, const uin
         if (first) {
             o[0] = 0x28; o[1] = 0xB5; o[2] = 0x2F; o[3] = 0xFD;                     // ZSTD_MAGICNUMBER 0xFD2FB528
             const uint32_t fcsCode = hs == 6u ? 0u : (hs == 7u ? 1u : 2u);
-            o[4] = (uint8_t)((fcsCode << 6) | (1u << 5));                            // single segment, no checksum, no dictID
+            o[4] = (uint8_t)((fcsCode << 6) | (1u << 5) | (hash ? 1u << 2 : 0u));    // single segment, [content checksum,] no dictID
             if (hs == 6u) o[5] = (uint8_t)frameLen;
             else if (hs == 7u) { uint32_t v = frameLen - 256u; o[5] = (uint8_t)v; o[6] = (uint8_t)(v >> 8); }
             else { o[5] = (uint8_t)frameLen; o[6] = (uint8_t)(frameLen >> 8); o[7] = (uint8_t)(frameLen >> 16); o[8] = (uint8_t)(frameLen >> 24); }
@@ -106,6 +117,11 @@ gc_zstd_emit_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, const uin
         const uint32_t bsz = p.compressed ? si.litSecSize + si.seqSecSize : blockLen;
         const uint32_t bh = (last ? 1u : 0u) | ((p.compressed ? 2u : 0u) << 1) | (bsz << 3);  // last block, type, size
         o[hs] = (uint8_t)bh; o[hs + 1u] = (uint8_t)(bh >> 8); o[hs + 2u] = (uint8_t)(bh >> 16);
+        if (hash && last) {                                                          // the frame's last four bytes (K4 counted them into p.size)
+            const uint32_t h = (uint32_t)hash[b / frameBlocks];
+            uint8_t* e = o + p.size - 4u;
+            e[0] = (uint8_t)h; e[1] = (uint8_t)(h >> 8); e[2] = (uint8_t)(h >> 16); e[3] = (uint8_t)(h >> 24);
+        }
     }
     uint8_t* pay = o + hs + 3u;
     if (p.compressed) {

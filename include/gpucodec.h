@@ -44,7 +44,7 @@ int         gc_ctx_create(gc_ctx** out, int device);
 void        gc_ctx_destroy(gc_ctx* ctx);
 const char* gc_last_error_message(const gc_ctx* ctx);
 
-/* worst-case compressed size for n input bytes (every block stored raw + frame overhead) */
+/* worst-case compressed size for n input bytes (every block stored raw + frame overhead, the seek table and the content checksums of the options below included) */
 size_t      gc_zstd_compress_bound(size_t n);
 
 /* Compress n bytes already resident in device memory into device memory.  Asynchronous on the context's
@@ -184,14 +184,29 @@ int         gc_multi_compress_host(gc_multi* m, int codec, const void* src, size
  *                           decoder skips it (ZstdDecoder.cpp:145-158 accepts skippable frames).
  *   GC_OPT_BROTLI_PLAIN     ONE brotli stream without the brotli-mt frame headers: what BROTLIMT_compressCCtx writes for threads == 0
  *                           (C/zstdmt/brotli-mt_compress.c:462-466) and what a bare .br file is.  Copies still stay inside their chunk.
+ *   GC_OPT_ZSTD_CHECKSUM    every zstd frame carries a content checksum: Content_Checksum_Flag in its header and, behind its last block, the low 32 bits of
+ *                           XXH64 (seed 0) of its content -- what the reference's bare-file handler asks for (ZstdHandler.cpp:276 "checksumFlag = 1", similar to
+ *                           the zstd client; ZSTD_writeEpilogue C/zstd/zstd_compress.c:5225-5232) and the only integrity check a bare .zst has (a 7z folder has
+ *                           the container's CRC: gc_pre.want_crc).  The hash is computed on the device from the call's input, beside the match finder.  With
+ *                           GC_OPT_ZSTD_SEEK_TABLE as well the table lists the checksums as the seekable format defines them: descriptor byte 0x80, entries
+ *                           of 12 bytes { compressed size, decompressed size, checksum }.  Every decoder here verifies the frames' checksums
+ *                           (gc_zstd_decompress_*: GC_ERR_CORRUPT).
  * Options hold for the following calls of the context (0 = off, the default). */
 #define GC_OPT_ZSTD_SEEK_TABLE 1
 #define GC_OPT_BROTLI_PLAIN    2
+#define GC_OPT_ZSTD_CHECKSUM   3
 /* flags of gc_host_begin / gc_codec_compress_host / gc_multi_compress_host for BROTLI: the call is one piece of ONE plain stream */
 #define GC_BROTLI_PLAIN     1u
 #define GC_BROTLI_NOT_FIRST 2u      /* ... and not its first piece: no stream header */
 #define GC_BROTLI_NOT_LAST  4u      /* ... and not its last piece: no closing (ISLAST) meta-block */
+/* flag of the same entry points (and of their _pre forms) for ZSTD: this call writes content checksums, as under GC_OPT_ZSTD_CHECKSUM; the context's own
+ * option comes back afterwards.  gc_multi_compress_host hands it to every piece (pieces are whole frames). */
+#define GC_ZSTD_CHECKSUM    8u
 int         gc_ctx_set_option(gc_ctx* ctx, int option, int value);
+/* HIP-event duration of the checksum kernel in the last gc_zstd_compress_device call (after gc_zstd_finish).  It runs on a stream of its own beside the
+ * other stages and joins in front of "plan", so it is inside ms[5] of gc_zstd_last_timing and in none of ms[0..4].  GC_ERR_PARAM if that call ran no
+ * checksum kernel (option off, or an empty input, whose checksum is a constant). */
+int         gc_zstd_checksum_timing(gc_ctx* ctx, float* ms);
 /* 1 in the test build of the library (csrc/libgpucodec_hooks.so: GC_* environment variables select code paths for the tests), 0 in the
  * shipped one, which reads no environment variable at all */
 int         gc_test_hooks_enabled(void);
@@ -199,6 +214,10 @@ int         gc_test_hooks_enabled(void);
 /* ---- CRC-32 of data that lies in device memory (C/7zCrc.c CrcCalc: polynomial 0xEDB88320, init and final XOR 0xFFFFFFFF).
  * Synchronous, on the current device's default stream. */
 int         gc_crc32_device(const void* d_src, size_t n, uint32_t* crc);
+
+/* ---- XXH64 of data that lies in device memory (C/zstd/xxhash.h XXH64(input, length, seed); zstd's content checksum is its low 32 bits with seed 0): the device
+ * code of GC_OPT_ZSTD_CHECKSUM over one "frame" of n bytes.  Any alignment of d_src.  Synchronous, on the current device's default stream. */
+int         gc_xxh64_device(const void* d_src, size_t n, uint64_t seed, uint64_t* hash);
 
 /* ---- Branch converters on data in device memory (the filters 7-Zip puts in front of a compressor for executables:
  * z7_BranchConv_ARM64_Enc / _Dec ... of C/Bra.c:75-709, called from NCompress::NBranch::CCoder::Filter, CPP/7zip/Compress/BranchMisc.cpp:21-26).
