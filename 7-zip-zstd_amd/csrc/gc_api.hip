@@ -10,8 +10,6 @@
 #include "gc_brotli.h"
 #include "gc_mf.h"
 #include "gc_zstd_dec.h"
-#include "gc_brotli_dec.h"
-#include "gc_lzma2_dec_work.h"
 #ifdef HIPEMU
 #include "hip_runtime_stub.h"
 #else
@@ -23,6 +21,9 @@
 #include <string.h>
 #include <new>
 #include "gc_host_stream.h"
+#include "gc_devbuf.h"
+#include "gc_brotli_dec.h"
+#include "gc_lzma2_dec_work.h"
 #ifdef GC_TEST_HOOKS
 #include <vector>
 #include <unistd.h>
@@ -107,53 +108,60 @@ extern "C" __global__ void gc_brotli_emit_kernel(const uint8_t*, uint64_t, const
                                                  uint32_t, uint32_t, const uint64_t*, uint8_t*);
 
 struct gc_ctx {
-    int device;
-    hipStream_t stream;       // main stream: K1 -> K2 -> (join) -> K4 -> K5
-    hipStream_t stream2;      // K3 runs here, concurrently with K2 (both only depend on K1); FLZMA2: model stage
-    hipStream_t stream3;      // FLZMA2: range-coder stage
-    hipEvent_t evPart[GC_MAX_PARTS][GC_PART_EVENTS];   // per input part: stage boundaries (see gc_flzma2_compress_device)
-    uint32_t nParts;
-    uint32_t optSeekTable, optBrotliPlain, optChecksum;   // gc_ctx_set_option
+    __attribute__((visibility("hidden"))) gc_ctx() = default;      // (hidden: the library exports its C functions, not these two)
+    __attribute__((visibility("hidden"))) ~gc_ctx() = default;
+    int device = 0;
+    hipStream_t stream = nullptr;       // main stream: K1 -> K2 -> (join) -> K4 -> K5
+    hipStream_t stream2 = nullptr;      // K3 runs here, concurrently with K2 (both only depend on K1); FLZMA2: model stage
+    hipStream_t stream3 = nullptr;      // FLZMA2: range-coder stage
+    hipEvent_t evPart[GC_MAX_PARTS][GC_PART_EVENTS] = {};   // per input part: stage boundaries (see gc_flzma2_compress_device)
+    uint32_t nParts = 0;
+    uint32_t optSeekTable = 0, optBrotliPlain = 0, optChecksum = 0;   // gc_ctx_set_option
     // zstd content checksums (GC_OPT_ZSTD_CHECKSUM): K0x reads nothing but the input and runs beside the whole pipeline.  It has a stream of its own (created with
     // the first call that wants checksums): stream2 / stream3 carry K3 / K2 in order, which would queue behind a hash that outlasts the finder in a small call.
-    hipStream_t streamHash; hipEvent_t evHash[2];      // K0x start, end
-    uint64_t* xxh; size_t xxhCap;                      // XXH64 per frame
-    bool hashTimed;                                    // the last compress call ran K0x (evHash brackets it)
-    uint32_t dbgFrameBlocks, dbgPartFrames;   // test hooks (env GC_FRAME_BLOCKS / GC_PART_FRAMES): small frames / parts so that
-                                              // the multi-frame and multi-part paths can be exercised on small inputs
-    hipEvent_t ev[8];         // 0 lz start, 1 lz end, 2 huf end, 3 seq start, 4 seq end, 5 plan start, 6 plan end, 7 emit end
-    char err[256];
-    // workspace, grown on demand
-    uint32_t capBlocks;
-    GcSeqRaw* seqRaw; uint8_t* lit; GcBlockMeta* meta;
-    uint64_t* seqPacked; uint32_t* seqOff; uint8_t* codes; uint16_t* stOut; GcSeqHist* seqHist; GcSeqTabG* seqTabs;
-    uint8_t* litSec; uint8_t* seqSec; GcSectionInfo* info; GcFramePlan* plan; uint64_t* result;
-    uint8_t* lzProps;         // FLZMA2: props byte per model segment (lc / lp chosen by L2), 128 KiB >> GC_LZMA_SEG_LOG_MIN of them per block
-    uint32_t* lzNM; GcLzmaChunkInfo* lzInfo; GcLzmaPlan* lzPlan; uint16_t* lzStream; size_t lzStreamCap;       // FLZMA2 path
-    uint64_t* lzM; size_t lzMCap; uint8_t* lzRcOut; size_t lzRcOutCap;     // item lists, range-coder staging (allocated on the first FLZMA2 call)
-    uint8_t* brStage; GcBrotliBlockInfo* brInfo; GcBrotliPlan* brPlan;    // BROTLI path
+    hipStream_t streamHash = nullptr; hipEvent_t evHash[2] = {};      // K0x start, end
+    GcBuf<uint64_t> xxh;                               // XXH64 per frame
+    bool hashTimed = false;                            // the last compress call ran K0x (evHash brackets it)
+    uint32_t dbgFrameBlocks = 0, dbgPartFrames = 0;   // test hooks (env GC_FRAME_BLOCKS / GC_PART_FRAMES): small frames / parts so that
+                                                      // the multi-frame and multi-part paths can be exercised on small inputs
+    hipEvent_t ev[8] = {};    // 0 lz start, 1 lz end, 2 huf end, 3 seq start, 4 seq end, 5 plan start, 6 plan end, 7 emit end
+    char err[256] = {};
+    // Device memory: every buffer is a GcBuf (gc_devbuf.h) that frees itself with the context.
+    // per-block workspace (workspace_resize): room for capBlocks blocks in each
+    uint32_t capBlocks = 0;
+    GcBuf<GcSeqRaw> seqRaw; GcBuf<uint8_t> lit; GcBuf<GcBlockMeta> meta;
+    GcBuf<uint64_t> seqPacked; GcBuf<uint32_t> seqOff; GcBuf<uint8_t> codes; GcBuf<uint16_t> stOut; GcBuf<GcSeqHist> seqHist; GcBuf<GcSeqTabG> seqTabs;
+    GcBuf<uint8_t> litSec, seqSec; GcBuf<GcSectionInfo> info; GcBuf<GcFramePlan> plan;
+    GcBuf<uint8_t> lzProps;   // FLZMA2: props byte per model segment (lc / lp chosen by L2), 128 KiB >> GC_LZMA_SEG_LOG_MIN of them per block
+    GcBuf<uint32_t> lzNM; GcBuf<GcLzmaChunkInfo> lzInfo; GcBuf<GcLzmaPlan> lzPlan;      // FLZMA2 path
+    GcBuf<uint8_t> brStage; GcBuf<GcBrotliBlockInfo> brInfo; GcBuf<GcBrotliPlan> brPlan;    // BROTLI path
+    GcBuf<uint16_t> lzStream; GcBuf<uint64_t> lzM; GcBuf<uint8_t> lzRcOut;     // FLZMA2: (p, bit) stream, item lists, range-coder staging (grown by the FLZMA2 calls)
+    GcBuf<uint64_t> result;   // [0] compressed size, [1] destination too small
     // windowed match finder (gc_mf.h): counts/offsets, partition starts, entry lists; grown on demand
-    uint32_t* mfTileWord; size_t mfTileWordCap;   // fused verify + parse: one word of counts per tile
-    uint32_t nCU; uint32_t* mfTicket;      // compute units of the device; ticket counters of the persistent launches (4 per part)
-    uint32_t* mfCnt; size_t mfCntCap; GcMfEntry* mfEnt; size_t mfEntCap; GcMfEntry* mfEnt2; size_t mfEnt2Cap; uint32_t* mfRec; size_t mfRecCap; uint32_t* mfRec2; size_t mfRec2Cap; uint32_t* mfChanged; size_t mfChangedCap;
-    uint16_t* mfRec3; size_t mfRec3Cap; uint32_t* mfDp; size_t mfDpCap; uint16_t* mfPrice; size_t mfPriceCap; uint32_t* mfWinCost; size_t mfWinCostCap; uint32_t* mfDpStat; size_t mfDpStatCap; uint8_t* mfLitPrice; size_t mfLitPriceCap;      // (+ W7L: literal price per position) W5s records, W7 records, price tables, W7 phase-A symbol counts
-    hipEvent_t evShort[GC_MAX_PARTS];       // W5s (near 2-3 byte candidates) runs beside the finder on stream2: done
-    hipEvent_t evMf[GC_MAX_PARTS][13];      // per part: W1 start, W1 end, W2 end, W3 end, W4 end, W5 end, W6 end; price-based parse: greedy W6 end, W5s end, W7 end;
-                                            // inside W5: first verify end, far pass end, deepen end
-    bool mfPriced;                          // the last call ran the price-based parse (events 7..9 are valid)
-    bool mfTimed; uint32_t mfParts;
-    int lastCodec;            // 0 zstd, 1 flzma2, 2 brotli: which kernels the events of the last call bracket
-    uint64_t* hostResult;     // pinned
-    // staging for the host-buffer entry point
+    GcBuf<uint32_t> mfTileWord;   // fused verify + parse: one word of counts per tile
+    uint32_t nCU = 0; GcBuf<uint32_t> mfTicket;      // compute units of the device; ticket counters of the persistent launches (4 per part)
+    GcBuf<uint32_t> mfCnt; GcBuf<GcMfEntry> mfEnt, mfEnt2; GcBuf<uint32_t> mfRec, mfRec2, mfChanged;
+    GcBuf<uint16_t> mfRec3; GcBuf<uint32_t> mfDp; GcBuf<uint16_t> mfPrice; GcBuf<uint32_t> mfWinCost, mfDpStat; GcBuf<uint8_t> mfLitPrice;      // (+ W7L: literal price per position) W5s records, W7 records, price tables, W7 phase-A symbol counts
+    hipEvent_t evShort[GC_MAX_PARTS] = {};       // W5s (near 2-3 byte candidates) runs beside the finder on stream2: done
+    hipEvent_t evMf[GC_MAX_PARTS][13] = {};      // per part: W1 start, W1 end, W2 end, W3 end, W4 end, W5 end, W6 end; price-based parse: greedy W6 end, W5s end, W7 end;
+                                                 // inside W5: first verify end, far pass end, deepen end
+    bool mfPriced = false;                       // the last call ran the price-based parse (events 7..9 are valid)
+    bool mfTimed = false; uint32_t mfParts = 0;
+    int lastCodec = 0;        // 0 zstd, 1 flzma2, 2 brotli: which kernels the events of the last call bracket
+    uint64_t* hostResult = nullptr;     // pinned
     GcBrDecWork brd;          // BROTLI decoder (gc_brotli_dec.hip)
     GcL2dWork l2d;            // LZMA2 decoder (gc_lzma2_dec.h)
-    uint8_t* dIn; size_t dInCap; uint8_t* dOut; size_t dOutCap; uint8_t* dPre; size_t dPreCap;      // (dPre: the pre-filtered input of gc_host_begin_pre)
-    bool pending; bool timed;
+    // staging for the host-buffer entry points (stage_reserve)
+    GcBuf<uint8_t> dIn, dOut, dPre;      // (dPre: the pre-filtered input of gc_host_begin_pre)
+    bool pending = false; bool timed = false;
     // zstd decoder (gc_zstd_dec.hip): per-workgroup literal / sequence workspace, frame table, per-frame results, ticket counter
-    uint8_t* zdLit; size_t zdLitCap; void* zdSeq; size_t zdSeqCap; GcZdFrame* zdFrames; size_t zdFramesCap; uint64_t* zdResult; uint64_t* zdTot;
-    GcZdBlock* zdBlocks; size_t zdBlocksCap; uint32_t* zdOrder; size_t zdOrderCap; uint32_t* zdReady; size_t zdReadyCap; uint32_t* zdTicket; GcZdPlace* zdPlace; size_t zdPlaceCap; uint32_t* zdPtr; size_t zdPtrCap; uint8_t* zdDone; size_t zdDoneCap; uint32_t* zdFerr; size_t zdFerrCap; uint32_t zdRounds; hipEvent_t zdEv[2]; float zdMs; float zdKms[4]; int zdSeqvState /* 0 not checked yet, 1 verified on this device, -1 wrong: the one-block-per-wave kernel is used */; bool zdSelfTest;   // last call: whole, and index / literals / sequences / execution kernels
-    unsigned long long* prof;  // device: GC_LZ_PHASES + GC_SEQ_PHASES cycle sums, only when profiling is on
-    bool profOn; uint32_t profBlocks;
+    GcBuf<uint8_t> zdLit; GcBuf<void> zdSeq; GcBuf<GcZdFrame> zdFrames; GcBuf<uint64_t> zdResult, zdTot;      // (the last three: room for the same number of frames)
+    GcBuf<GcZdBlock> zdBlocks; GcBuf<uint32_t> zdOrder, zdReady, zdTicket; GcBuf<GcZdPlace> zdPlace; GcBuf<uint32_t> zdPtr; GcBuf<uint8_t> zdDone; GcBuf<uint32_t> zdFerr;
+    uint32_t zdRounds = 0; hipEvent_t zdEv[2] = {}; float zdMs = 0.f; float zdKms[4] = {};      // last call: whole, and index / literals / sequences / execution kernels
+    int zdSeqvState = 0;      // 0 not checked yet, 1 verified on this device, -1 wrong: the one-block-per-wave kernel is used
+    bool zdSelfTest = false;
+    GcBuf<unsigned long long> prof;  // GC_LZ_PHASES + GC_SEQ_PHASES cycle sums, only when profiling is on
+    bool profOn = false; uint32_t profBlocks = 0;
 };
 
 // Test hooks (environment variables) exist only in the TEST build of this file (-DGC_TEST_HOOKS: csrc/libgpucodec_hooks.so and the emulator
@@ -196,7 +204,6 @@ extern "C" size_t gc_zstd_compress_bound(size_t n)
          + nb * 8;                                              // (+ the optional content checksums: 4 bytes behind every frame and 4 more per seek-table entry, every block a frame of its own at worst)
 }
 
-static void free_workspace(gc_ctx* c);
 void gc_brd_release(GcBrDecWork* w);
 int gc_brd_decode(hipStream_t st, GcBrDecWork* w, const uint8_t* d_src, const gc_brotli_chunk* chunks, size_t nChunks, uint8_t* d_dst, size_t dstCap, size_t* produced, char* err, size_t errCap);
 void gc_l2d_release(GcL2dWork* w);
@@ -216,7 +223,6 @@ extern "C" int gc_ctx_create(gc_ctx** out, int device)
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return GC_ERR_NO_DEVICE;     // kernels are built for gfx950 only
     gc_ctx* c = new (std::nothrow) gc_ctx();
     if (!c) return GC_ERR_NOMEM;
-    memset(c, 0, sizeof(*c));
     c->device = device;
     c->nCU = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 256u;
     // every failure below releases what has been created so far (ctx_release skips what is still null)
@@ -228,9 +234,9 @@ extern "C" int gc_ctx_create(gc_ctx** out, int device)
         if (rc == GC_OK && hipEventCreate(&c->evShort[p]) != hipSuccess) rc = GC_ERR_HIP;
         for (uint32_t i = 0; rc == GC_OK && i < GC_PART_EVENTS; i++) if (hipEventCreate(&c->evPart[p][i]) != hipSuccess) rc = GC_ERR_HIP;
     }
-    if (rc == GC_OK && hipMalloc((void**)&c->prof, (GC_LZ_PHASES + GC_SEQ_PHASES) * sizeof(unsigned long long)) != hipSuccess) rc = GC_ERR_NOMEM;
-    if (rc == GC_OK && (hipMalloc((void**)&c->mfTicket, GC_MAX_PARTS * 16u * sizeof(uint32_t)) != hipSuccess || hipMemsetAsync(c->mfTicket, 0, GC_MAX_PARTS * 16u * sizeof(uint32_t), c->stream) != hipSuccess)) rc = GC_ERR_NOMEM;
-    if (rc == GC_OK && (hipMalloc((void**)&c->result, 16) != hipSuccess || hipHostMalloc((void**)&c->hostResult, 16 + GC_MAX_PARTS * 16u * sizeof(uint32_t)) != hipSuccess)) rc = GC_ERR_NOMEM;      // (+ a copy of the ticket / watchdog words)
+    if (rc == GC_OK && gc_buf_reserve(c->prof, (GC_LZ_PHASES + GC_SEQ_PHASES) * sizeof(unsigned long long)) != GC_OK) rc = GC_ERR_NOMEM;
+    if (rc == GC_OK && gc_buf_reserve(c->mfTicket, GC_MAX_PARTS * 16u * sizeof(uint32_t), 0, 0, 0, c->stream) != GC_OK) rc = GC_ERR_NOMEM;      // (starts zeroed)
+    if (rc == GC_OK && (gc_buf_reserve(c->result, 16) != GC_OK || hipHostMalloc((void**)&c->hostResult, 16 + GC_MAX_PARTS * 16u * sizeof(uint32_t)) != hipSuccess)) rc = GC_ERR_NOMEM;      // (+ a copy of the ticket / watchdog words)
     if (rc != GC_OK) { ctx_release(c); return rc; }
     c->dbgFrameBlocks = dbg_frame_blocks(); c->dbgPartFrames = 0;
     c->l2d.nCU = c->nCU;
@@ -239,30 +245,15 @@ extern "C" int gc_ctx_create(gc_ctx** out, int device)
     return GC_OK;
 }
 
-static void free_workspace(gc_ctx* c)
-{
-    hipFree(c->seqRaw); hipFree(c->lit); hipFree(c->meta); hipFree(c->seqPacked); hipFree(c->seqOff); hipFree(c->codes);
-    hipFree(c->stOut); hipFree(c->seqHist); hipFree(c->seqTabs); hipFree(c->litSec); hipFree(c->seqSec); hipFree(c->info); hipFree(c->plan);
-    hipFree(c->brStage); hipFree(c->brInfo); hipFree(c->brPlan); c->brStage = nullptr; c->brInfo = nullptr; c->brPlan = nullptr;
-    hipFree(c->lzProps); c->lzProps = nullptr; hipFree(c->lzNM); hipFree(c->lzInfo); hipFree(c->lzPlan); hipFree(c->lzStream); c->lzStream = nullptr; c->lzStreamCap = 0; c->lzNM = nullptr; c->lzInfo = nullptr; c->lzPlan = nullptr;
-    hipFree(c->lzM); c->lzM = nullptr; c->lzMCap = 0; hipFree(c->lzRcOut); c->lzRcOut = nullptr; c->lzRcOutCap = 0;
-    c->seqRaw = nullptr; c->lit = nullptr; c->meta = nullptr; c->seqPacked = nullptr; c->seqOff = nullptr; c->codes = nullptr;
-    c->stOut = nullptr; c->seqHist = nullptr; c->seqTabs = nullptr; c->litSec = nullptr; c->seqSec = nullptr; c->info = nullptr; c->plan = nullptr; c->capBlocks = 0;
-}
-
 static void ctx_release(gc_ctx* c)
 {
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    free_workspace(c);
     if (c->streamHash) hipStreamSynchronize(c->streamHash);
-    hipFree(c->xxh);
-    hipFree(c->prof); hipFree(c->mfTicket); hipFree(c->result); if (c->hostResult) hipHostFree(c->hostResult); hipFree(c->dIn); hipFree(c->dOut); hipFree(c->dPre);
+    if (c->hostResult) hipHostFree(c->hostResult);
     gc_brd_release(&c->brd);
     gc_l2d_release(&c->l2d);
-    hipFree(c->zdLit); hipFree(c->zdSeq); hipFree(c->zdFrames); hipFree(c->zdResult); hipFree(c->zdTot); hipFree(c->zdBlocks); hipFree(c->zdOrder); hipFree(c->zdReady); hipFree(c->zdTicket); hipFree(c->zdPlace); hipFree(c->zdPtr); hipFree(c->zdDone); hipFree(c->zdFerr);
     for (int i = 0; i < 2; i++) if (c->zdEv[i]) hipEventDestroy(c->zdEv[i]);
-    hipFree(c->mfTileWord); hipFree(c->mfCnt); hipFree(c->mfEnt); hipFree(c->mfEnt2); hipFree(c->mfRec); hipFree(c->mfRec2); hipFree(c->mfChanged); hipFree(c->mfRec3); hipFree(c->mfDp); hipFree(c->mfPrice); hipFree(c->mfWinCost); hipFree(c->mfDpStat); hipFree(c->mfLitPrice);
     for (int i = 0; i < 8; i++) if (c->ev[i]) hipEventDestroy(c->ev[i]);
     for (uint32_t p = 0; p < GC_MAX_PARTS; p++) {
         for (int i = 0; i < 13; i++) if (c->evMf[p][i]) hipEventDestroy(c->evMf[p][i]);
@@ -274,7 +265,7 @@ static void ctx_release(gc_ctx* c)
     if (c->stream3) hipStreamDestroy(c->stream3);
     if (c->stream2) hipStreamDestroy(c->stream2);
     if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                 // (the device buffers free themselves: gc_devbuf.h)
 }
 
 extern "C" void gc_ctx_destroy(gc_ctx* c)
@@ -296,37 +287,31 @@ extern "C" int gc_ctx_set_option(gc_ctx* c, int option, int value)
 extern "C" const char* gc_last_error_message(const gc_ctx* c) { return c ? c->err : "no context"; }
 extern "C" void* gc_ctx_stream(gc_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
+// The per-block workspace: room for nBlocks blocks in every row, or none of it (nBlocks == 0, and after a failed growth).  capBlocks says what the rows hold --
+// it is also the stride of lzProps' second half (gc_flzma2_compress_device: segKind).
+static int workspace_resize(gc_ctx* c, uint32_t nBlocks)
+{
+    const size_t ms = GC_MAX_SEQ_PER_BLOCK;
+    const struct { GcBufRaw& buf; size_t perBlock; } rows[] = {
+        { c->seqRaw, ms * sizeof(GcSeqRaw) }, { c->lit, GC_ZSTD_BLOCK_MAX }, { c->meta, sizeof(GcBlockMeta) }, { c->seqPacked, ms * sizeof(uint64_t) }, { c->seqOff, ms * sizeof(uint32_t) },
+        { c->codes, ms * 3 }, { c->stOut, GC_SEQ_ST_STRIDE * 3 * sizeof(uint16_t) }, { c->seqHist, sizeof(GcSeqHist) }, { c->seqTabs, 3 * sizeof(GcSeqTabG) },
+        { c->litSec, GC_LITSEC_STRIDE }, { c->seqSec, GC_SEQSEC_STRIDE }, { c->info, sizeof(GcSectionInfo) }, { c->plan, sizeof(GcFramePlan) },
+        { c->brStage, GC_BR_STAGE_STRIDE }, { c->brInfo, sizeof(GcBrotliBlockInfo) }, { c->brPlan, sizeof(GcBrotliPlan) },
+        { c->lzProps, 2u * (GC_ZSTD_BLOCK_MAX >> GC_LZMA_SEG_LOG_MIN) },      // (second half: LZMA / stored per model segment, gc_lzma2_segkind_kernel)
+        { c->lzNM, sizeof(uint32_t) }, { c->lzInfo, GC_LZMA_RC_PER_BLOCK * sizeof(GcLzmaChunkInfo) }, { c->lzPlan, GC_LZMA_RC_PER_BLOCK * sizeof(GcLzmaPlan) } };
+    c->capBlocks = 0;
+    for (auto& r : rows) {
+        if (!nBlocks) gc_buf_release(r.buf);
+        else if (gc_buf_reserve(r.buf, nBlocks * r.perBlock) != GC_OK) { workspace_resize(c, 0); return GC_ERR_NOMEM; }
+    }
+    c->capBlocks = nBlocks;
+    return GC_OK;
+}
 static int ensure_workspace(gc_ctx* c, uint32_t nBlocks)
 {
     if (nBlocks <= c->capBlocks) return GC_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_workspace(c);
-    const size_t nb = nBlocks, ms = GC_MAX_SEQ_PER_BLOCK;
-    if (hipMalloc((void**)&c->seqRaw, nb * ms * sizeof(GcSeqRaw)) != hipSuccess ||
-        hipMalloc((void**)&c->lit, nb * GC_ZSTD_BLOCK_MAX) != hipSuccess ||
-        hipMalloc((void**)&c->meta, nb * sizeof(GcBlockMeta)) != hipSuccess ||
-        hipMalloc((void**)&c->seqPacked, nb * ms * sizeof(uint64_t)) != hipSuccess ||
-        hipMalloc((void**)&c->seqOff, nb * ms * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void**)&c->codes, nb * ms * 3) != hipSuccess ||
-        hipMalloc((void**)&c->stOut, nb * GC_SEQ_ST_STRIDE * 3 * sizeof(uint16_t)) != hipSuccess ||
-        hipMalloc((void**)&c->seqHist, nb * sizeof(GcSeqHist)) != hipSuccess ||
-        hipMalloc((void**)&c->seqTabs, nb * 3 * sizeof(GcSeqTabG)) != hipSuccess ||
-        hipMalloc((void**)&c->litSec, nb * GC_LITSEC_STRIDE) != hipSuccess ||
-        hipMalloc((void**)&c->seqSec, nb * GC_SEQSEC_STRIDE) != hipSuccess ||
-        hipMalloc((void**)&c->info, nb * sizeof(GcSectionInfo)) != hipSuccess ||
-        hipMalloc((void**)&c->plan, nb * sizeof(GcFramePlan)) != hipSuccess ||
-        hipMalloc((void**)&c->brStage, nb * GC_BR_STAGE_STRIDE) != hipSuccess ||
-        hipMalloc((void**)&c->brInfo, nb * sizeof(GcBrotliBlockInfo)) != hipSuccess ||
-        hipMalloc((void**)&c->brPlan, nb * sizeof(GcBrotliPlan)) != hipSuccess ||
-        hipMalloc((void**)&c->lzProps, 2u * nb * (GC_ZSTD_BLOCK_MAX >> GC_LZMA_SEG_LOG_MIN)) != hipSuccess ||      // (second half: LZMA / stored per model segment, gc_lzma2_segkind_kernel)
-        hipMalloc((void**)&c->lzNM, nb * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void**)&c->lzInfo, nb * GC_LZMA_RC_PER_BLOCK * sizeof(GcLzmaChunkInfo)) != hipSuccess ||
-        hipMalloc((void**)&c->lzPlan, nb * GC_LZMA_RC_PER_BLOCK * sizeof(GcLzmaPlan)) != hipSuccess) {
-        free_workspace(c);
-        snprintf(c->err, sizeof(c->err), "workspace allocation for %u blocks failed", nBlocks);
-        return GC_ERR_NOMEM;
-    }
-    c->capBlocks = nBlocks;
+    if (workspace_resize(c, nBlocks) != GC_OK) { snprintf(c->err, sizeof(c->err), "workspace allocation for %u blocks failed", nBlocks); return GC_ERR_NOMEM; }
     return GC_OK;
 }
 
@@ -505,17 +490,22 @@ static uint32_t lz_frame_arg(int codec, int level, uint32_t nBlocks, uint32_t db
 // frameBlocks == 1: K1, the block-local finder (hash tables in LDS, matches stay inside the 128 KiB block).
 // frameBlocks  > 1: W1..W6, the windowed finder (gc_lz_window.hip): matches reach back to the start of the frame.
 // Both leave the same interface behind: seqRaw / lit / meta per block.
-static int mf_grow(gc_ctx* c, void** p, size_t* cap, size_t needBytes, const char* what)
+// The arrays of the finder, the parses and the FLZMA2 stages grow to exactly what a call needs (0 bytes: not needed by this call).  If any of them has to grow, the main stream
+// is waited for first: kernels of the last call may still read the old buffers.
+struct GcWsNeed { GcBufRaw& buf; size_t bytes; const char* what; };
+static int mf_reserve(gc_ctx* c, const GcWsNeed* rows, size_t nRows)
 {
-    if (needBytes <= *cap) return GC_OK;
-    void* np = nullptr;                                            // the old buffer stays valid if the growth fails
-    if (hipMalloc(&np, needBytes) != hipSuccess) {
-        hipFree(*p); *p = nullptr; *cap = 0;                       // second try with the old one released first
-        if (hipMalloc(&np, needBytes) != hipSuccess) { snprintf(c->err, sizeof(c->err), "workspace (%s) of %zu bytes failed", what, needBytes); return GC_ERR_NOMEM; }
+    bool grow = false;
+    for (size_t i = 0; i < nRows; i++) grow = grow || rows[i].bytes > rows[i].buf.cap;
+    if (!grow) return GC_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    uint32_t poison = 0;                                           // test hook: the workspace starts filled with this byte -- what a recycled allocation holds is not zeros
+    const int fill = gc_env_u32("GC_POISON_WORKSPACE", 0u, 255u, &poison) ? (int)poison : -1;
+    for (size_t i = 0; i < nRows; i++) {
+        const int rc = gc_buf_reserve(rows[i].buf, rows[i].bytes, 0, 0, fill, c->stream);
+        if (rc == GC_ERR_NOMEM) snprintf(c->err, sizeof(c->err), "workspace (%s) of %zu bytes failed", rows[i].what, rows[i].bytes);
+        if (rc != GC_OK) return rc;
     }
-    hipFree(*p); *p = np; *cap = needBytes;
-    { uint32_t poison = 0; if (gc_env_u32("GC_POISON_WORKSPACE", 0u, 255u, &poison) && hipMemsetAsync(np, (int)poison, needBytes, c->stream) != hipSuccess) return GC_ERR_HIP; }   // test hook: the
-                                                                   // finder's workspace starts filled with this byte -- what a recycled allocation holds is not zeros
     return GC_OK;
 }
 
@@ -544,27 +534,13 @@ static int ensure_finder_workspace(gc_ctx* c, const GcLzPlan& plan, size_t n, ui
     const size_t needRec = (size_t)g.nBlocks * GC_ZSTD_BLOCK_MAX * sizeof(uint32_t);
     const size_t needPrice = (size_t)g.nBlocks * GC_PRICE_WORDS * sizeof(uint16_t);
     const size_t needTileWord = ((size_t)g.nTiles + 64u) * sizeof(uint32_t);
-    if (needTileWord > c->mfTileWordCap || needCnt > c->mfCntCap || needEnt > c->mfEntCap || needEnt > c->mfEnt2Cap || needRec > c->mfRecCap || ((plan.searchDepth || plan.shortPass) && (needRec > c->mfRec2Cap || needRec / 32u + 64u > c->mfChangedCap)) ||
-        (plan.priceParse && (needRec / 2u > c->mfRec3Cap || needRec > c->mfDpCap || needPrice > c->mfPriceCap || (size_t)g.nBlocks * 128u > c->mfWinCostCap || (size_t)g.nBlocks * GC_DPS_WORDS * 4u > c->mfDpStatCap || needRec / 4u > c->mfLitPriceCap))) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        int rc;
-        if ((rc = mf_grow(c, (void**)&c->mfTileWord, &c->mfTileWordCap, needTileWord, "tile counts")) != GC_OK) return rc;
-        if ((rc = mf_grow(c, (void**)&c->mfCnt, &c->mfCntCap, needCnt, "offsets")) != GC_OK) return rc;
-        if ((rc = mf_grow(c, (void**)&c->mfEnt, &c->mfEntCap, needEnt, "entries")) != GC_OK) return rc;
-        if ((rc = mf_grow(c, (void**)&c->mfEnt2, &c->mfEnt2Cap, needEnt, "linked entries")) != GC_OK) return rc;
-        if ((rc = mf_grow(c, (void**)&c->mfRec, &c->mfRecCap, needRec, "records")) != GC_OK) return rc;
-        if ((plan.searchDepth || plan.shortPass) && (rc = mf_grow(c, (void**)&c->mfRec2, &c->mfRec2Cap, needRec, "deepened records")) != GC_OK) return rc;
-        if ((plan.searchDepth || plan.shortPass) && (rc = mf_grow(c, (void**)&c->mfChanged, &c->mfChangedCap, needRec / 32u + 64u, "changed-record bitmap")) != GC_OK) return rc;
-        if (plan.priceParse) {
-            if ((rc = mf_grow(c, (void**)&c->mfRec3, &c->mfRec3Cap, needRec / 2u, "short candidates")) != GC_OK) return rc;
-            if ((rc = mf_grow(c, (void**)&c->mfDp, &c->mfDpCap, needRec, "price-parse records")) != GC_OK) return rc;
-            if ((rc = mf_grow(c, (void**)&c->mfPrice, &c->mfPriceCap, needPrice, "price tables")) != GC_OK) return rc;
-            if ((rc = mf_grow(c, (void**)&c->mfWinCost, &c->mfWinCostCap, (size_t)g.nBlocks * 128u, "window costs")) != GC_OK) return rc;
-            if ((rc = mf_grow(c, (void**)&c->mfDpStat, &c->mfDpStatCap, (size_t)g.nBlocks * GC_DPS_WORDS * 4u, "path symbol counts")) != GC_OK) return rc;
-            if ((rc = mf_grow(c, (void**)&c->mfLitPrice, &c->mfLitPriceCap, needRec / 4u, "literal prices")) != GC_OK) return rc;
-        }
-    }
-    return GC_OK;
+    const size_t deep = (plan.searchDepth || plan.shortPass) ? 1u : 0u, priced = plan.priceParse ? 1u : 0u;
+    const GcWsNeed rows[] = {
+        { c->mfTileWord, needTileWord, "tile counts" }, { c->mfCnt, needCnt, "offsets" }, { c->mfEnt, needEnt, "entries" }, { c->mfEnt2, needEnt, "linked entries" }, { c->mfRec, needRec, "records" },
+        { c->mfRec2, deep * needRec, "deepened records" }, { c->mfChanged, deep * (needRec / 32u + 64u), "changed-record bitmap" },
+        { c->mfRec3, priced * (needRec / 2u), "short candidates" }, { c->mfDp, priced * needRec, "price-parse records" }, { c->mfPrice, priced * needPrice, "price tables" },
+        { c->mfWinCost, priced * g.nBlocks * 128u, "window costs" }, { c->mfDpStat, priced * g.nBlocks * GC_DPS_WORDS * 4u, "path symbol counts" }, { c->mfLitPrice, priced * (needRec / 4u), "literal prices" } };
+    return mf_reserve(c, rows, sizeof(rows) / sizeof(rows[0]));
 }
 
 // Match finder for one part of the input: `src` / `n` are the part, blk0 its first block (a multiple of frameBlocks: parts are
@@ -829,11 +805,9 @@ extern "C" int gc_zstd_compress_device(gc_ctx* c, const void* d_src, size_t n, v
             if (hipStreamCreate(&c->streamHash) != hipSuccess) { c->streamHash = nullptr; snprintf(c->err, sizeof(c->err), "no stream for the content checksums"); return GC_ERR_HIP; }
             for (int i = 0; i < 2; i++) if (!c->evHash[i]) HIPCHK(c, hipEventCreate(&c->evHash[i]));
         }
-        if (hFrames > c->xxhCap) {
+        if ((size_t)hFrames * sizeof(uint64_t) > c->xxh.cap) {
             HIPCHK(c, hipStreamSynchronize(c->streamHash));
-            hipFree(c->xxh); c->xxh = nullptr; c->xxhCap = 0;
-            if (hipMalloc((void**)&c->xxh, (size_t)hFrames * sizeof(uint64_t)) != hipSuccess) { c->xxh = nullptr; snprintf(c->err, sizeof(c->err), "workspace allocation for %u frame checksums failed", hFrames); return GC_ERR_NOMEM; }
-            c->xxhCap = hFrames;
+            if (gc_buf_reserve(c->xxh, (size_t)hFrames * sizeof(uint64_t)) != GC_OK) { snprintf(c->err, sizeof(c->err), "workspace allocation for %u frame checksums failed", hFrames); return GC_ERR_NOMEM; }
         }
         HIPCHK(c, hipStreamWaitEvent(c->streamHash, c->ev[0], 0));
         HIPCHK(c, hipEventRecord(c->evHash[0], c->streamHash));
@@ -862,7 +836,7 @@ extern "C" int gc_zstd_compress_device(gc_ctx* c, const void* d_src, size_t n, v
         const size_t off = (size_t)blk0 * GC_ZSTD_BLOCK_MAX;
         const size_t len = (size_t)framesPerPart * zFrameBlocks * GC_ZSTD_BLOCK_MAX < n - off ? (size_t)framesPerPart * zFrameBlocks * GC_ZSTD_BLOCK_MAX : n - off;
         const uint32_t pBlocks = gc_num_blocks(len);
-        rc = launch_finder_part(c, plan, c->stream, p, src + off, len, zArg, blk0, c->profOn ? c->prof : nullptr);
+        rc = launch_finder_part(c, plan, c->stream, p, src + off, len, zArg, blk0, c->profOn ? (unsigned long long*)c->prof : nullptr);
         if (rc != GC_OK) return rc;
         HIPCHK(c, hipEventRecord(c->evPart[p][0], c->stream));                                 // finder of this part done
         if (p + 1u == nParts || blk0 + pBlocks >= nBlocks) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
@@ -897,7 +871,7 @@ extern "C" int gc_zstd_compress_device(gc_ctx* c, const void* d_src, size_t n, v
     HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
     GC_LAUNCH(gc_zstd_emit_kernel, nBlocks + (c->optSeekTable ? 1u : 0u), 256, c->stream, src, (uint64_t)n, (const uint8_t*)c->litSec, (const uint8_t*)c->seqSec,
               (const GcSectionInfo*)c->info, (const GcFramePlan*)c->plan, (const uint64_t*)c->result, nBlocks, zFrameBlocks, (uint8_t*)d_dst,
-              (const uint64_t*)(c->optChecksum ? c->xxh : nullptr));
+              c->optChecksum ? (const uint64_t*)c->xxh : nullptr);
     HIPCHK(c, hipEventRecord(c->ev[7], c->stream));
     HIPCHK(c, hipGetLastError());
     c->pending = true; c->timed = true; c->lastCodec = 0;
@@ -1043,12 +1017,8 @@ extern "C" int gc_flzma2_compress_device(gc_ctx* c, const void* d_src, size_t n,
         // item lists; range-coder staging
         const size_t needStream = (size_t)nSegs * GC_LZMA_STREAM_WORDS(segLog) * sizeof(uint16_t);
         const size_t needM = (size_t)nBlocks * GC_LZMA_MAX_ITEMS * sizeof(uint64_t), needRc = (size_t)nRc * GC_LZMA_RC_STRIDE;
-        if (needStream > c->lzStreamCap || needM > c->lzMCap || needRc > c->lzRcOutCap) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if ((rc = mf_grow(c, (void**)&c->lzStream, &c->lzStreamCap, needStream, "LZMA stream")) != GC_OK) return rc;
-            if ((rc = mf_grow(c, (void**)&c->lzM, &c->lzMCap, needM, "LZMA items")) != GC_OK) return rc;
-            if ((rc = mf_grow(c, (void**)&c->lzRcOut, &c->lzRcOutCap, needRc, "range-coder staging")) != GC_OK) return rc;
-        }
+        const GcWsNeed rows[] = { { c->lzStream, needStream, "LZMA stream" }, { c->lzM, needM, "LZMA items" }, { c->lzRcOut, needRc, "range-coder staging" } };
+        if ((rc = mf_reserve(c, rows, 3)) != GC_OK) return rc;
     }
     const GcLzPlan plan = with_hooks(flzma2_plan(level));
     const uint32_t fArg = lz_frame_arg(GC_CODEC_FLZMA2, level, nBlocks, c->dbgFrameBlocks);    // what the finder takes: overlapping frames from level 5
@@ -1113,7 +1083,7 @@ extern "C" int gc_flzma2_compress_device(gc_ctx* c, const void* d_src, size_t n,
                   (const uint32_t*)(c->lzNM + blk0), segLog, (uint32_t)(off != 0u ? 1u : 0u),
                   c->lzStream + (size_t)blk0 * segPerBlock * GC_LZMA_STREAM_WORDS(segLog), c->lzInfo + (size_t)blk0 * GC_LZMA_RC_PER_BLOCK,
                   (const uint32_t*)((plan.priceParse && MF_F(fArg) > 1u) ? c->mfWinCost + (size_t)blk0 * 32u : nullptr),
-                  c->profOn ? c->prof : nullptr, mergeWords, wordCap, rep4, c->lzProps + (size_t)blk0 * segPerBlock, litSel, segMerge, mergeBudget);
+                  c->profOn ? (unsigned long long*)c->prof : nullptr, mergeWords, wordCap, rep4, c->lzProps + (size_t)blk0 * segPerBlock, litSel, segMerge, mergeBudget);
         HIPCHK(c, hipEventRecord(ev[4], c->stream2));
         // stage 3 (stream3): range coder
         HIPCHK(c, hipStreamWaitEvent(c->stream3, ev[4], 0));
@@ -1206,7 +1176,7 @@ extern "C" int gc_brotli_compress_device(gc_ctx* c, const void* d_src, size_t n,
     uint32_t brCtx = level >= 5 ? 1u : 0u;                     // literal context modelling from quality 5 (the reference: MIN_QUALITY_FOR_CONTEXT_MODELING, C/brotli/enc/quality.h): B1 chooses one tree or thirteen per meta-block
     gc_env_u32("GC_BR_CTX", 0u, 1u, &brCtx);                                                    // test hook
     GC_LAUNCH(gc_brotli_block_kernel, nBlocks, 256, c->stream, src, (uint64_t)n, (const GcSeqRaw*)c->seqRaw, (const uint8_t*)c->lit,
-              (const GcBlockMeta*)c->meta, c->seqPacked, c->seqOff, bpc, c->optBrotliPlain, brRepSub, brCtx, (uint32_t*)c->brStage, c->brInfo);
+              (const GcBlockMeta*)c->meta, c->seqPacked, c->seqOff, bpc, c->optBrotliPlain, brRepSub, brCtx, (uint32_t*)c->brStage.p, c->brInfo);
     HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     GC_LAUNCH(gc_brotli_plan_kernel, 1, 1024, c->stream, (const GcBrotliBlockInfo*)c->brInfo, nBlocks, bpc, (uint64_t)dstCap, c->brPlan, c->result);
     HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
@@ -1243,6 +1213,13 @@ extern "C" size_t gc_codec_compress_bound(int codec, size_t n)
     return codec == GC_CODEC_ZSTD ? gc_zstd_compress_bound(n) : (codec == GC_CODEC_FLZMA2 ? gc_flzma2_compress_bound(n) : gc_brotli_compress_bound(n));
 }
 
+// Staging of the host-buffer entry points: room for inBytes in dIn and for outBytes in dOut.  The decoders and filters read and write a few bytes past the end: a padding
+// behind each that the capacity does not count (the compressor's dOut is its bound as it stands).  No message of its own: the callers never had one.
+static int stage_reserve(gc_ctx* c, size_t inBytes, size_t outBytes, size_t outPad = 64u)
+{
+    return (gc_buf_reserve(c->dIn, inBytes, 64u) != GC_OK || gc_buf_reserve(c->dOut, outBytes, outPad) != GC_OK) ? GC_ERR_NOMEM : GC_OK;
+}
+
 struct GcStreamScope { hipStream_t prev; explicit GcStreamScope(hipStream_t st) : prev(gc_tls_stream) { gc_tls_stream = st; } ~GcStreamScope() { gc_tls_stream = prev; } };      // (gc_host_stream.h: the stand-alone entry points run on this context's stream while in scope)
 extern "C" int gc_crc32_device(const void* d_src, size_t n, uint32_t* crc);
 extern "C" int gc_bra_convert_device(int kind, const void* d_src, void* d_dst, size_t n, uint32_t pc, int encoding, size_t* processed);
@@ -1259,8 +1236,7 @@ extern "C" int gc_host_begin_pre(gc_ctx* c, int codec, const void* src, size_t n
     if (dl && (pre->delta < 1u || pre->delta > 256u)) return GC_ERR_PARAM;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bound = gc_codec_compress_bound(codec, n);
-    if (n > c->dInCap) { hipFree(c->dIn); c->dIn = nullptr; c->dInCap = 0; if (hipMalloc((void**)&c->dIn, n + 64) != hipSuccess) return GC_ERR_NOMEM; c->dInCap = n; }
-    if (bound > c->dOutCap) { hipFree(c->dOut); c->dOut = nullptr; c->dOutCap = 0; if (hipMalloc((void**)&c->dOut, bound) != hipSuccess) return GC_ERR_NOMEM; c->dOutCap = bound; }
+    if (stage_reserve(c, n, bound, 0u) != GC_OK) return GC_ERR_NOMEM;
     if (n) HIPCHK(c, hipMemcpyAsync(c->dIn, src, n, hipMemcpyHostToDevice, c->stream));
     const uint8_t* d_in = c->dIn;
     if (pre) { pre->crc = 0; pre->processed = 0; }
@@ -1268,7 +1244,7 @@ extern "C" int gc_host_begin_pre(gc_ctx* c, int codec, const void* src, size_t n
         const GcStreamScope onMine(c->stream);                       // the CRC and the converters run on this context's stream (round 6: they used the null stream and waited for the whole device), in order behind the copy above
         if (pre->want_crc) { const int rc = gc_crc32_device(c->dIn, n, &pre->crc); if (rc != GC_OK) { snprintf(c->err, sizeof(c->err), "CRC of the input failed on the device"); return rc; } }
         if (flt) {
-            if (n > c->dPreCap) { hipFree(c->dPre); c->dPre = nullptr; c->dPreCap = 0; if (hipMalloc((void**)&c->dPre, n + 64) != hipSuccess) return GC_ERR_NOMEM; c->dPreCap = n; }
+            if (gc_buf_reserve(c->dPre, n, 64u) != GC_OK) return GC_ERR_NOMEM;
             size_t done = 0; int rc;
             if (x86) { uint32_t st; memcpy(&st, pre->state, 4); rc = gc_bra_x86_convert_device(c->dIn, c->dPre, n, pre->pc, 1, &st, &done); memcpy(pre->state, &st, 4); }
             else if (dl) { rc = gc_delta_convert_device(c->dIn, c->dPre, n, pre->delta, 1, pre->state); done = n; }
@@ -1281,20 +1257,20 @@ extern "C" int gc_host_begin_pre(gc_ctx* c, int codec, const void* src, size_t n
     if (codec == GC_CODEC_BROTLI && (flags & GC_BROTLI_PLAIN)) {      // per-call form of GC_OPT_BROTLI_PLAIN (pieces of one stream); the context's own option comes back afterwards
         const uint32_t keep = c->optBrotliPlain;
         c->optBrotliPlain = (flags & 7u) | 1u;
-        const int rc = gc_brotli_compress_device(c, d_in, n, c->dOut, c->dOutCap, level);
+        const int rc = gc_brotli_compress_device(c, d_in, n, c->dOut, c->dOut.cap, level);
         c->optBrotliPlain = keep;
         return rc;
     }
     if (codec == GC_CODEC_ZSTD && (flags & GC_ZSTD_CHECKSUM)) {       // per-call form of GC_OPT_ZSTD_CHECKSUM, likewise
         const uint32_t keep = c->optChecksum;
         c->optChecksum = 1u;
-        const int rc = gc_zstd_compress_device(c, d_in, n, c->dOut, c->dOutCap, level);
+        const int rc = gc_zstd_compress_device(c, d_in, n, c->dOut, c->dOut.cap, level);
         c->optChecksum = keep;
         return rc;
     }
-    return codec == GC_CODEC_ZSTD ? gc_zstd_compress_device(c, d_in, n, c->dOut, c->dOutCap, level)
-         : codec == GC_CODEC_FLZMA2 ? gc_flzma2_compress_device(c, d_in, n, c->dOut, c->dOutCap, level, flags)
-                                    : gc_brotli_compress_device(c, d_in, n, c->dOut, c->dOutCap, level);
+    return codec == GC_CODEC_ZSTD ? gc_zstd_compress_device(c, d_in, n, c->dOut, c->dOut.cap, level)
+         : codec == GC_CODEC_FLZMA2 ? gc_flzma2_compress_device(c, d_in, n, c->dOut, c->dOut.cap, level, flags)
+                                    : gc_brotli_compress_device(c, d_in, n, c->dOut, c->dOut.cap, level);
 }
 extern "C" int gc_host_begin(gc_ctx* c, int codec, const void* src, size_t n, int level, unsigned flags) { return gc_host_begin_pre(c, codec, src, n, level, flags, nullptr); }
 
@@ -1302,7 +1278,7 @@ extern "C" int gc_host_size(gc_ctx* c, size_t* compressedSize) { return gc_zstd_
 
 extern "C" int gc_host_fetch(gc_ctx* c, void* dst, size_t size)
 {
-    if (!c || (!dst && size) || size > c->dOutCap) return GC_ERR_PARAM;
+    if (!c || (!dst && size) || size > c->dOut.cap) return GC_ERR_PARAM;
     HIPCHK(c, hipSetDevice(c->device));
     if (size) { HIPCHK(c, hipMemcpyAsync(dst, c->dOut, size, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); }
     return GC_OK;
@@ -1356,14 +1332,13 @@ extern "C" void gc_zstd_dec_launch_spread(hipStream_t st, const uint8_t* src, ui
 extern "C" void gc_zstd_dec_launch_chase(hipStream_t st, uint8_t* dstBatch, uint32_t* ptr, uint32_t n, uint32_t hops, uint8_t* pieceDone, uint32_t* counter);
 extern "C" void gc_zstd_dec_launch_finish(hipStream_t st, const uint8_t* src, const uint8_t* dst, const GcZdFrame* frames, uint32_t nFrames, uint64_t* result, const uint32_t* ferr);
 
-static int zd_grow(gc_ctx* c, void** p, size_t* cap, size_t need)
+// the zstd decoder's arrays grow with an eighth to spare: batches of about the same size follow each other
+static int zd_reserve(gc_ctx* c, GcBufRaw& b, size_t need)
 {
-    if (need <= *cap) return GC_OK;
-    hipFree(*p); *p = nullptr; *cap = 0;
-    const size_t want = need + need / 8u + 4096u;
-    if (hipMalloc(p, want) != hipSuccess) { *p = nullptr; snprintf(c->err, sizeof(c->err), "decoder workspace: out of device memory (%zu bytes)", want); return GC_ERR_NOMEM; }
-    *cap = want;
-    return GC_OK;
+    const size_t slack = need / 8u + 4096u;
+    const int rc = gc_buf_reserve(b, need, 0, slack);
+    if (rc != GC_OK) snprintf(c->err, sizeof(c->err), "decoder workspace: out of device memory (%zu bytes)", need + slack);
+    return rc;
 }
 
 // Run-time check of the sequences kernel that takes six blocks per wave (gc_zstd_dec_seqv_kernel).  Its lanes exchange values through quad-permute DPP moves
@@ -1427,7 +1402,7 @@ extern "C" int gc_zstd_decompress_device(gc_ctx* c, const void* d_src, size_t n,
     uint64_t* res = (uint64_t*)malloc(nFrames * 16u);           // per frame results; also the (literal bytes, sequence records) totals of the index pass
     if (!h || !res) { free(h); free(res); return GC_ERR_NOMEM; }
     int rc = GC_OK;
-    if (!c->zdTicket && hipMalloc((void**)&c->zdTicket, 8) != hipSuccess) rc = GC_ERR_NOMEM;      // [0] the execution kernel's frame ticket, [1] the chase kernel's count
+    if (gc_buf_reserve(c->zdTicket, 8) != GC_OK) rc = GC_ERR_NOMEM;      // [0] the execution kernel's frame ticket, [1] the chase kernel's count
     for (int i = 0; i < 2 && rc == GC_OK; i++) if (!c->zdEv[i] && hipEventCreate(&c->zdEv[i]) != hipSuccess) rc = GC_ERR_HIP;
     // test hook GC_ZD_PROF=1: shader cycles of the execution kernel's phases (thread 0's view, summed over blocks) on stderr
     unsigned long long* zdProf = nullptr;
@@ -1455,14 +1430,12 @@ extern "C" int gc_zstd_decompress_device(gc_ctx* c, const void* d_src, size_t n,
         }
         if (rc != GC_OK) break;
         const size_t cnt = j - i;
-        if (cnt > c->zdFramesCap) {
-            hipFree(c->zdFrames); hipFree(c->zdResult); hipFree(c->zdTot); c->zdFrames = nullptr; c->zdResult = nullptr; c->zdTot = nullptr; c->zdFramesCap = 0;
-            const size_t cap = cnt + cnt / 2u + 64u;
-            if (hipMalloc((void**)&c->zdFrames, cap * sizeof(GcZdFrame)) != hipSuccess || hipMalloc((void**)&c->zdResult, cap * 8u) != hipSuccess ||
-                hipMalloc((void**)&c->zdTot, cap * 16u) != hipSuccess) { rc = GC_ERR_NOMEM; break; }
-            c->zdFramesCap = cap;
+        {   // frame table, results and totals grow together, with half as many frames to spare
+            const size_t spare = cnt / 2u + 64u;
+            if (gc_buf_reserve(c->zdFrames, cnt * sizeof(GcZdFrame), 0, spare * sizeof(GcZdFrame)) != GC_OK || gc_buf_reserve(c->zdResult, cnt * 8u, 0, spare * 8u) != GC_OK ||
+                gc_buf_reserve(c->zdTot, cnt * 16u, 0, spare * 16u) != GC_OK) { rc = GC_ERR_NOMEM; break; }
         }
-        if ((rc = zd_grow(c, (void**)&c->zdBlocks, &c->zdBlocksCap, (size_t)nBlocks * sizeof(GcZdBlock))) != GC_OK) break;      // capacity in bytes
+        if ((rc = zd_reserve(c, c->zdBlocks, (size_t)nBlocks * sizeof(GcZdBlock))) != GC_OK) break;      // capacity in bytes
         // index pass: block table, per-frame workspace needs
         if (hipMemcpyAsync(c->zdFrames, h + i, cnt * sizeof(GcZdFrame), hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = GC_ERR_HIP; break; }
         hipEventRecord(c->zdEv[0], c->stream);
@@ -1473,8 +1446,8 @@ extern "C" int gc_zstd_decompress_device(gc_ctx* c, const void* d_src, size_t n,
         }
         uint64_t litTot = 0, seqTot = 0;
         for (size_t k = 0; k < cnt; k++) { h[i + k].litBase = litTot; h[i + k].seqBase = seqTot; litTot += res[2u * k]; seqTot += res[2u * k + 1u]; }
-        if ((rc = zd_grow(c, (void**)&c->zdLit, &c->zdLitCap, (size_t)litTot + 64u)) != GC_OK) break;
-        if ((rc = zd_grow(c, &c->zdSeq, &c->zdSeqCap, (size_t)seqTot * 16u + 64u)) != GC_OK) break;
+        if ((rc = zd_reserve(c, c->zdLit, (size_t)litTot + 64u)) != GC_OK) break;
+        if ((rc = zd_reserve(c, c->zdSeq, (size_t)seqTot * 16u + 64u)) != GC_OK) break;
         if (hipMemcpyAsync(c->zdFrames, h + i, cnt * sizeof(GcZdFrame), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
             hipMemsetAsync(c->zdTicket, 0, 4, c->stream) != hipSuccess) { rc = GC_ERR_HIP; break; }
         // literals on stream2, sequences on the main stream (both only need the block table), the execution kernel on stream3.  With few frames
@@ -1501,8 +1474,8 @@ extern "C" int gc_zstd_decompress_device(gc_ctx* c, const void* d_src, size_t n,
         else if (c->zdSeqvState < 0) seqSeveral = 0;             // it decoded the known frame wrongly on this device / build: not used
         { uint32_t v = 0; if (gc_env_u32("GC_ZD_WIDE", 0, 1, &v)) wide = v != 0u; }
         if (wide) overlap = false;
-        if ((rc = zd_grow(c, (void**)&c->zdOrder, &c->zdOrderCap, (size_t)nBlocks * 4u)) != GC_OK) break;
-        if ((rc = zd_grow(c, (void**)&c->zdReady, &c->zdReadyCap, (size_t)nBlocks * 4u)) != GC_OK) break;
+        if ((rc = zd_reserve(c, c->zdOrder, (size_t)nBlocks * 4u)) != GC_OK) break;
+        if ((rc = zd_reserve(c, c->zdReady, (size_t)nBlocks * 4u)) != GC_OK) break;
         {
             uint32_t* ord = (uint32_t*)malloc((size_t)nBlocks * 4u);
             if (!ord) { rc = GC_ERR_NOMEM; break; }
@@ -1528,27 +1501,24 @@ extern "C" int gc_zstd_decompress_device(gc_ctx* c, const void* d_src, size_t n,
         gc_zstd_dec_launch_sequences(c->stream, (const uint8_t*)d_src, n, c->zdFrames, c->zdBlocks, (uint32_t)nBlocks, c->zdSeq, zdProf, c->zdOrder, c->zdReady, seqSeveral);
         hipEventRecord(c->evPart[1][1], c->stream);
         hipStreamWaitEvent(c->stream, c->evPart[0][1], 0);
+        uint64_t extent = 0, padded = 0;                       // wide execution: content bytes of the batch, from its first byte; rounded up to 4 KiB
         if (wide) {
             hipEventRecord(c->evPart[1][3], c->stream);
-            if ((rc = zd_grow(c, (void**)&c->zdPlace, &c->zdPlaceCap, (size_t)nBlocks * sizeof(GcZdPlace))) != GC_OK) break;
-            if ((rc = zd_grow(c, (void**)&c->zdFerr, &c->zdFerrCap, cnt * 4u)) != GC_OK) break;
+            if ((rc = zd_reserve(c, c->zdPlace, (size_t)nBlocks * sizeof(GcZdPlace))) != GC_OK) break;
+            if ((rc = zd_reserve(c, c->zdFerr, cnt * 4u)) != GC_OK) break;
             gc_zstd_dec_launch_place(c->stream, c->zdFrames, (uint32_t)cnt, c->zdBlocks, dstCap, c->zdPlace, c->zdResult, c->zdFerr);
             if (hipMemcpyAsync(res, c->zdResult, cnt * 8u, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
                 snprintf(c->err, sizeof(c->err), "decode kernels failed: %s", hipGetErrorString(hipGetLastError())); rc = GC_ERR_HIP; break;
             }
-            uint64_t extent = 0;                                   // content bytes of the batch, from its first byte
             for (size_t k = 0; k < cnt; k++) { const uint64_t e = h[i + k].dstOff - h[i].dstOff + (res[k] & 0x00FFFFFFFFFFFFFFull); if (e > extent) extent = e; }
-            const uint64_t padded = (extent + 4095u) & ~4095ull;
+            padded = (extent + 4095u) & ~4095ull;
             uint32_t noRoom = 0; gc_env_u32("GC_ZD_WIDE_NOMEM", 1u, 1u, &noRoom);               // test hook: as if the workspace could not be had
             if (extent > GC_ZD_WIDE_MAX) noRoom = 1;               // (one frame beyond the reach of the 32-bit positions)
-            if (noRoom || zd_grow(c, (void**)&c->zdPtr, &c->zdPtrCap, (size_t)padded * 4u + 16u) != GC_OK || zd_grow(c, (void**)&c->zdDone, &c->zdDoneCap, (size_t)(padded / 1024u) + 16u) != GC_OK) {
+            if (noRoom || zd_reserve(c, c->zdPtr, (size_t)padded * 4u + 16u) != GC_OK || zd_reserve(c, c->zdDone, (size_t)(padded / 1024u) + 16u) != GC_OK) {
                 wide = false; c->err[0] = 0;                       // no room for the pointers: the frame kernel does it
             }
         }
         if (wide) {
-            uint64_t extent = 0;
-            for (size_t k = 0; k < cnt; k++) { const uint64_t e = h[i + k].dstOff - h[i].dstOff + (res[k] & 0x00FFFFFFFFFFFFFFull); if (e > extent) extent = e; }
-            const uint64_t padded = (extent + 4095u) & ~4095ull;
             if (hipMemsetAsync(c->zdPtr, 0xFF, (size_t)padded * 4u, c->stream) != hipSuccess || hipMemsetAsync(c->zdDone, 0, (size_t)(padded / 1024u) + 16u, c->stream) != hipSuccess) { rc = GC_ERR_HIP; break; }
             gc_zstd_dec_launch_spread(c->stream, (const uint8_t*)d_src, n, (uint8_t*)d_dst, c->zdFrames, c->zdBlocks, (uint32_t)nBlocks, c->zdPlace, c->zdLit, litTot + 64u, c->zdSeq,
                                       c->zdPtr, h[i].dstOff, c->zdFerr);
@@ -1635,8 +1605,7 @@ extern "C" int gc_filter_host(gc_ctx* c, int kind, void* data, size_t n, uint32_
     if (dl && (delta < 1u || delta > 256u)) return GC_ERR_PARAM;
     HIPCHK(c, hipSetDevice(c->device));
     if (!n) return GC_OK;
-    if (n > c->dInCap) { hipFree(c->dIn); c->dIn = nullptr; c->dInCap = 0; if (hipMalloc((void**)&c->dIn, n + 64) != hipSuccess) return GC_ERR_NOMEM; c->dInCap = n; }
-    if (n > c->dOutCap) { hipFree(c->dOut); c->dOut = nullptr; c->dOutCap = 0; if (hipMalloc((void**)&c->dOut, n + 64) != hipSuccess) return GC_ERR_NOMEM; c->dOutCap = n; }
+    if (stage_reserve(c, n, n) != GC_OK) return GC_ERR_NOMEM;
     const GcStreamScope onMine(c->stream);                           // (the converters run on this context's stream, in order with the copies)
     HIPCHK(c, hipMemcpyAsync(c->dIn, data, n, hipMemcpyHostToDevice, c->stream));
     size_t done = 0; int rc;
@@ -1663,6 +1632,19 @@ extern "C" int gc_zstd_decompress_kernel_timing(gc_ctx* c, float ms[4]) { if (!c
 
 extern "C" int gc_zstd_decompress_wide_rounds(gc_ctx* c, unsigned* rounds) { if (!c || !rounds) return GC_ERR_PARAM; *rounds = c->zdRounds; return GC_OK; }
 
+// What the three host-buffer decoders do once the scan of `src` has come out as rc: stage inBytes of it, decode(&produced) from dIn into dOut (room for outBytes), copy
+// the produced bytes to dst and wait for them.  The caller frees its scan table afterwards.
+template <typename Decode> static int decode_staged(gc_ctx* c, int rc, const void* src, size_t inBytes, void* dst, size_t outBytes, size_t* outSize, Decode decode)
+{
+    if (rc == GC_OK) rc = stage_reserve(c, inBytes, outBytes);
+    size_t produced = 0;
+    if (rc == GC_OK && hipMemcpyAsync(c->dIn, src, inBytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = GC_ERR_HIP;
+    if (rc == GC_OK) rc = decode(&produced);
+    if (rc == GC_OK && produced && (hipMemcpyAsync(dst, c->dOut, produced, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) rc = GC_ERR_HIP;
+    if (rc == GC_OK && outSize) *outSize = produced;
+    return rc;
+}
+
 extern "C" int gc_zstd_decompress_host(gc_ctx* c, const void* src, size_t n, void* dst, size_t dstCap, size_t* outSize)
 {
     if (!c || (!src && n) || (!dst && dstCap)) return GC_ERR_PARAM;
@@ -1677,27 +1659,28 @@ extern "C" int gc_zstd_decompress_host(gc_ctx* c, const void* src, size_t n, voi
     uint64_t total = 0;
     rc = gc_zstd_scan_frames(src, n, fr, nFrames, &nFrames, &total);
     if (rc == GC_OK && total != ~0ull && total > dstCap) { snprintf(c->err, sizeof(c->err), "destination too small: need %llu bytes", (unsigned long long)total); rc = GC_ERR_DST_SMALL; }
-    if (rc == GC_OK && n > c->dInCap) { hipFree(c->dIn); c->dIn = nullptr; c->dInCap = 0; if (hipMalloc((void**)&c->dIn, n + 64) != hipSuccess) rc = GC_ERR_NOMEM; else c->dInCap = n; }
     const size_t need = total != ~0ull ? (size_t)total : dstCap;
-    if (rc == GC_OK && need > c->dOutCap) { hipFree(c->dOut); c->dOut = nullptr; c->dOutCap = 0; if (hipMalloc((void**)&c->dOut, need + 64) != hipSuccess) rc = GC_ERR_NOMEM; else c->dOutCap = need; }
-    size_t produced = 0;
-    if (rc == GC_OK && hipMemcpyAsync(c->dIn, src, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = GC_ERR_HIP;
-    if (rc == GC_OK) rc = gc_zstd_decompress_device(c, c->dIn, n, c->dOut, need, fr, nFrames, &produced);
-    if (rc == GC_OK && produced && (hipMemcpyAsync(dst, c->dOut, produced, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) rc = GC_ERR_HIP;
+    rc = decode_staged(c, rc, src, n, dst, need, outSize, [&](size_t* produced) { return gc_zstd_decompress_device(c, c->dIn, n, c->dOut, need, fr, nFrames, produced); });
     free(fr);
-    if (rc == GC_OK && outSize) *outSize = produced;
     return rc;
 }
 
 // ---- BROTLI decoder (gc_brotli_dec.hip): the context's stream and buffers around gc_brd_decode
+static void brd_hooks(gc_ctx* c)      // test hooks: a smaller LDS arena, one kernel instance whatever the number of chunks
+{
+#ifdef GC_TEST_HOOKS
+    const char* e = getenv("GC_BRD_LDS"); c->brd.ldsCap = e ? (uint32_t)atoi(e) : 0u;
+    e = getenv("GC_BRD_INSTANCE"); c->brd.instance = e ? (uint32_t)atoi(e) : 0u;
+#else
+    (void)c;
+#endif
+}
 extern "C" int gc_brotli_decompress_device(gc_ctx* c, const void* d_src, size_t n, void* d_dst, size_t dstCap, const gc_brotli_chunk* chunks, size_t nChunks, size_t* outSize)
 {
     if (!c || (!d_src && n) || (!chunks && nChunks) || !outSize) return GC_ERR_PARAM;
     HIPCHK(c, hipSetDevice(c->device));
     *outSize = 0;
-#ifdef GC_TEST_HOOKS
-    { const char* e = getenv("GC_BRD_LDS"); c->brd.ldsCap = e ? (uint32_t)atoi(e) : 0u; e = getenv("GC_BRD_INSTANCE"); c->brd.instance = e ? (uint32_t)atoi(e) : 0u; }
-#endif
+    brd_hooks(c);
     for (size_t i = 0; i < nChunks; i++) if (chunks[i].src_off > n || chunks[i].src_size > n - chunks[i].src_off) { snprintf(c->err, sizeof(c->err), "brotli chunk %zu lies outside the %zu input bytes", i, n); return GC_ERR_PARAM; }
     return gc_brd_decode(c->stream, &c->brd, (const uint8_t*)d_src, chunks, nChunks, (uint8_t*)d_dst, dstCap, outSize, c->err, sizeof(c->err));
 }
@@ -1723,17 +1706,9 @@ extern "C" int gc_brotli_decompress_host(gc_ctx* c, const void* src, size_t n, v
         if (!ch) return GC_ERR_NOMEM;
         rc = gc_brotli_scan_prefix(src, n, ch, nChunks, &nChunks, nullptr, &consumed);
     }
-    if (rc == GC_OK && n > c->dInCap) { hipFree(c->dIn); c->dIn = nullptr; c->dInCap = 0; if (hipMalloc((void**)&c->dIn, n + 64) != hipSuccess) rc = GC_ERR_NOMEM; else c->dInCap = n; }
-    if (rc == GC_OK && dstCap > c->dOutCap) { hipFree(c->dOut); c->dOut = nullptr; c->dOutCap = 0; if (hipMalloc((void**)&c->dOut, dstCap + 64) != hipSuccess) rc = GC_ERR_NOMEM; else c->dOutCap = dstCap; }
-    size_t produced = 0;
-    if (rc == GC_OK && hipMemcpyAsync(c->dIn, src, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = GC_ERR_HIP;
-#ifdef GC_TEST_HOOKS
-    { const char* e = getenv("GC_BRD_LDS"); c->brd.ldsCap = e ? (uint32_t)atoi(e) : 0u; e = getenv("GC_BRD_INSTANCE"); c->brd.instance = e ? (uint32_t)atoi(e) : 0u; }
-#endif
-    if (rc == GC_OK) rc = gc_brd_decode(c->stream, &c->brd, c->dIn, ch, nChunks, c->dOut, dstCap, &produced, c->err, sizeof(c->err));
-    if (rc == GC_OK && produced && (hipMemcpyAsync(dst, c->dOut, produced, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) rc = GC_ERR_HIP;
+    brd_hooks(c);
+    rc = decode_staged(c, rc, src, n, dst, dstCap, outSize, [&](size_t* produced) { return gc_brd_decode(c->stream, &c->brd, c->dIn, ch, nChunks, c->dOut, dstCap, produced, c->err, sizeof(c->err)); });
     if (ch != &one) free(ch);
-    if (rc == GC_OK && outSize) *outSize = produced;
     return rc;
 }
 extern "C" int gc_brotli_decompress_timing(gc_ctx* c, float* ms) { if (!c || !ms) return GC_ERR_PARAM; *ms = c->brd.ms; return GC_OK; }
@@ -1763,15 +1738,10 @@ extern "C" int gc_lzma2_decompress_host(gc_ctx* c, const void* src, size_t n, vo
     gc_lzma2_unit* un = (gc_lzma2_unit*)malloc(nUnits * sizeof(gc_lzma2_unit));
     if (!un) return GC_ERR_NOMEM;
     rc = gc_lzma2_scan_prefix(src, n, un, nUnits, &nUnits, &total, &consumed, &ended);
-    if (rc == GC_OK && consumed > c->dInCap) { hipFree(c->dIn); c->dIn = nullptr; c->dInCap = 0; if (hipMalloc((void**)&c->dIn, consumed + 64) != hipSuccess) rc = GC_ERR_NOMEM; else c->dInCap = consumed; }
-    if (rc == GC_OK && total > c->dOutCap) { hipFree(c->dOut); c->dOut = nullptr; c->dOutCap = 0; if (hipMalloc((void**)&c->dOut, (size_t)total + 64) != hipSuccess) rc = GC_ERR_NOMEM; else c->dOutCap = (size_t)total; }
-    size_t produced = 0;
-    if (rc == GC_OK && hipMemcpyAsync(c->dIn, src, consumed, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = GC_ERR_HIP;
     l2d_hooks(c);
-    if (rc == GC_OK) rc = gc_l2d_decode(c->stream, &c->l2d, c->dIn, consumed, un, nUnits, c->dOut, (size_t)total, dictProp, &produced, c->err, sizeof(c->err));
-    if (rc == GC_OK && produced && (hipMemcpyAsync(dst, c->dOut, produced, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) rc = GC_ERR_HIP;
+    rc = decode_staged(c, rc, src, consumed, dst, (size_t)total, outSize, [&](size_t* produced) {      // (the bytes up to the end marker, not n)
+        return gc_l2d_decode(c->stream, &c->l2d, c->dIn, consumed, un, nUnits, c->dOut, (size_t)total, dictProp, produced, c->err, sizeof(c->err)); });
     free(un);
-    if (rc == GC_OK && outSize) *outSize = produced;
     return rc;
 }
 extern "C" int gc_lzma2_decompress_timing(gc_ctx* c, float* ms) { if (!c || !ms) return GC_ERR_PARAM; *ms = c->l2d.ms; return GC_OK; }

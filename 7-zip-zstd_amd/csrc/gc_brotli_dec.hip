@@ -24,7 +24,6 @@
 #include "gc_common.h"
 #include "gc_device.h"
 #include "gc_brotli.h"
-#include "gc_brotli_dec.h"
 #ifdef HIPEMU
 #include "hip_runtime_stub.h"
 #include <stdio.h>
@@ -35,6 +34,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "gc_host_stream.h"
+#include "gc_brotli_dec.h"
 #include "gc_brotli_transforms.h"
 
 // status of one chunk
@@ -947,24 +947,11 @@ extern "C" int gc_brotli_dec_set_dictionary(const void* data, size_t n)
 }
 extern "C" int gc_brotli_dec_has_dictionary(void) { return gBrDict != nullptr; }
 
-static bool brd_grow(uint8_t** p, size_t* cap, size_t need)
+void gc_brd_release(GcBrDecWork* w)      // (the events: the buffers free themselves with the context)
 {
-    if (need <= *cap) return true;
-    if (*p) hipFree(*p);
-    *p = nullptr; *cap = 0;
-    if (hipMalloc((void**)p, need + 64) != hipSuccess) return false;
-    *cap = need;
-    return true;
-}
-void gc_brd_release(GcBrDecWork* w)
-{
-    if (w->stage) hipFree(w->stage);
-    if (w->pages) hipFree(w->pages);
-    if (w->meta) hipFree(w->meta);
-    if (w->dict) hipFree(w->dict);
     if (w->ev0) hipEventDestroy((hipEvent_t)w->ev0);
     if (w->ev1) hipEventDestroy((hipEvent_t)w->ev1);
-    memset(w, 0, sizeof(*w));
+    w->ev0 = w->ev1 = nullptr;
 }
 // d_src / d_dst: device memory; chunks: host memory (as the scan returned them).  Synchronous (the sizes are read back).
 int gc_brd_decode(hipStream_t st, GcBrDecWork* w, const uint8_t* d_src, const gc_brotli_chunk* chunks, size_t nChunks, uint8_t* d_dst, size_t dstCap, size_t* produced, char* err, size_t errCap)
@@ -983,9 +970,9 @@ int gc_brd_decode(hipStream_t st, GcBrDecWork* w, const uint8_t* d_src, const gc
     const size_t oChunks = 0, oRes = (nChunks * sizeof(GcBrDecChunk) + 63u) & ~(size_t)63u, oOffs = oRes + ((nChunks * sizeof(GcBrDecResult) + 63u) & ~(size_t)63u),
                  oTot = oOffs + ((nChunks * 8u + 63u) & ~(size_t)63u), oCur = oTot + 64u, metaBytes = oCur + 64u;
     int rc = GC_OK;
-    if (!brd_grow(&w->stage, &w->stageCap, (size_t)stageBytes + 64u) || !brd_grow(&w->meta, &w->metaCap, metaBytes)) rc = GC_ERR_NOMEM;
+    if (gc_buf_reserve(w->stage, (size_t)stageBytes + 64u, 64u) != GC_OK || gc_buf_reserve(w->meta, metaBytes, 64u) != GC_OK) rc = GC_ERR_NOMEM;
     if (rc == GC_OK && gBrDict && (!w->dict || w->dictStamp != gBrDictStamp)) {
-        if (!w->dict && hipMalloc((void**)&w->dict, 122784u + 64u) != hipSuccess) rc = GC_ERR_NOMEM;
+        if (gc_buf_reserve(w->dict, 122784u, 64u) != GC_OK) rc = GC_ERR_NOMEM;
         else if (hipMemcpyAsync(w->dict, gBrDict, 122784u, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = GC_ERR_HIP;
         w->dictStamp = gBrDictStamp;
     }
@@ -994,23 +981,19 @@ int gc_brd_decode(hipStream_t st, GcBrDecWork* w, const uint8_t* d_src, const gc
     for (int attempt = 0; attempt < 2 && rc == GC_OK; attempt++) {
         // pages: a chunk whose meta-block does not fit LDS takes one; few streams need any (the reference's qualities 10-11), so the pool starts small
         const uint32_t wantPages = attempt == 0 ? (uint32_t)(nChunks < 64u ? nChunks : 64u) : (uint32_t)nChunks;
-        if (w->nPages < wantPages) {
-            if (w->pages) hipFree(w->pages);
-            w->pages = nullptr; w->nPages = 0;
-            if (hipMalloc((void**)&w->pages, (size_t)wantPages * BRD_PAGE) != hipSuccess) { rc = GC_ERR_NOMEM; break; }
-            w->nPages = wantPages;
-        }
+        if (gc_buf_reserve(w->pages, (size_t)wantPages * BRD_PAGE) != GC_OK) { rc = GC_ERR_NOMEM; break; }
+        const uint32_t nPages = (uint32_t)(w->pages.cap / BRD_PAGE);
         if (hipMemcpyAsync(w->meta + oChunks, hc, nChunks * sizeof(GcBrDecChunk), hipMemcpyHostToDevice, st) != hipSuccess || hipMemsetAsync(w->meta + oCur, 0, 64, st) != hipSuccess) { rc = GC_ERR_HIP; break; }
-        GcBrDict dict; dict.words = gBrDict ? w->dict : nullptr;
+        GcBrDict dict; dict.words = gBrDict ? (uint8_t*)w->dict : nullptr;
         const uint32_t grid = (uint32_t)(nChunks < BRD_MAX_WAVES ? nChunks : BRD_MAX_WAVES);
         hipEventRecord((hipEvent_t)w->ev0, st);
         const GcBrDecChunk* dc = (const GcBrDecChunk*)(w->meta + oChunks); uint32_t* cur = (uint32_t*)(w->meta + oCur); GcBrDecResult* res = (GcBrDecResult*)(w->meta + oRes);
         const uint32_t inst = w->instance ? w->instance : (nChunks <= 256u ? 1u : (nChunks <= 512u ? 2u : (nChunks <= 1024u ? 3u : 4u)));
         const uint32_t lc = w->ldsCap ? w->ldsCap : ~0u;
-        if (inst == 1u) GC_LAUNCH(gc_brotli_dec_kernel_a, grid, 64, st, d_src, dc, (uint32_t)nChunks, w->stage, w->pages, w->nPages, cur, res, dict, lc);
-        else if (inst == 2u) GC_LAUNCH(gc_brotli_dec_kernel_b, grid, 64, st, d_src, dc, (uint32_t)nChunks, w->stage, w->pages, w->nPages, cur, res, dict, lc);
-        else if (inst == 3u) GC_LAUNCH(gc_brotli_dec_kernel_c, grid, 64, st, d_src, dc, (uint32_t)nChunks, w->stage, w->pages, w->nPages, cur, res, dict, lc);
-        else GC_LAUNCH(gc_brotli_dec_kernel_d, grid, 64, st, d_src, dc, (uint32_t)nChunks, w->stage, w->pages, w->nPages, cur, res, dict, lc);
+        if (inst == 1u) GC_LAUNCH(gc_brotli_dec_kernel_a, grid, 64, st, d_src, dc, (uint32_t)nChunks, w->stage, w->pages, nPages, cur, res, dict, lc);
+        else if (inst == 2u) GC_LAUNCH(gc_brotli_dec_kernel_b, grid, 64, st, d_src, dc, (uint32_t)nChunks, w->stage, w->pages, nPages, cur, res, dict, lc);
+        else if (inst == 3u) GC_LAUNCH(gc_brotli_dec_kernel_c, grid, 64, st, d_src, dc, (uint32_t)nChunks, w->stage, w->pages, nPages, cur, res, dict, lc);
+        else GC_LAUNCH(gc_brotli_dec_kernel_d, grid, 64, st, d_src, dc, (uint32_t)nChunks, w->stage, w->pages, nPages, cur, res, dict, lc);
         GC_LAUNCH(gc_brotli_dec_plan_kernel, 1, 1024, st, (const GcBrDecResult*)(w->meta + oRes), (uint32_t)nChunks, (uint64_t)dstCap, (uint64_t*)(w->meta + oOffs), (uint64_t*)(w->meta + oTot));
         const uint32_t pieces = (maxHint + 65535u) >> 16;
         if (pieces) GC_LAUNCH(gc_brotli_dec_pack_kernel, (uint32_t)nChunks * pieces, 256, st, w->stage, (const GcBrDecChunk*)(w->meta + oChunks), (const GcBrDecResult*)(w->meta + oRes),
@@ -1018,7 +1001,7 @@ int gc_brd_decode(hipStream_t st, GcBrDecWork* w, const uint8_t* d_src, const gc
         hipEventRecord((hipEvent_t)w->ev1, st);
         if (hipMemcpyAsync(tot, w->meta + oTot, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { rc = GC_ERR_HIP; break; }
         hipEventElapsedTime(&w->ms, (hipEvent_t)w->ev0, (hipEvent_t)w->ev1);
-        if (tot[1] != BRD_LIMIT || w->nPages >= nChunks) break;   // (a second round with a page for every chunk)
+        if (tot[1] != BRD_LIMIT || nPages >= nChunks) break;   // (a second round with a page for every chunk)
     }
     free(hc);
     if (rc != GC_OK) return rc;

@@ -30,7 +30,6 @@
 #include "gpucodec.h"
 #include "gc_common.h"
 #include "gc_device.h"
-#include "gc_lzma2_dec_work.h"
 #ifdef HIPEMU
 #include "hip_runtime_stub.h"
 #else
@@ -43,6 +42,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include "gc_lzma2_dec_work.h"
 
 // status of one unit
 #define L2D_OK          0u
@@ -443,12 +443,11 @@ extern "C" int gc_lzma2_scan_prefix(const void* src, size_t n, gc_lzma2_unit* un
     return GC_OK;
 }
 
-void gc_l2d_release(GcL2dWork* w)
+void gc_l2d_release(GcL2dWork* w)      // (the events: the buffers free themselves with the context)
 {
-    if (w->meta) hipFree(w->meta);
     if (w->ev0) hipEventDestroy((hipEvent_t)w->ev0);
     if (w->ev1) hipEventDestroy((hipEvent_t)w->ev1);
-    memset(w, 0, sizeof(*w));
+    w->ev0 = w->ev1 = nullptr;
 }
 // d_src / d_dst: device memory; units: host memory (as the scan returned them).  Synchronous (the units' results are read back).
 int gc_l2d_decode(hipStream_t st, GcL2dWork* w, const uint8_t* d_src, size_t n, const gc_lzma2_unit* units, size_t nUnits, uint8_t* d_dst, size_t dstCap, unsigned dictProp,
@@ -490,12 +489,7 @@ int gc_l2d_decode(hipStream_t st, GcL2dWork* w, const uint8_t* d_src, size_t n, 
         std::sort(ho, ho + nA, larger);
         std::sort(ho + nA, ho + nUnits, larger);
     }
-    int rc = GC_OK;
-    if (metaBytes > w->metaCap) {
-        if (w->meta) hipFree(w->meta);
-        w->meta = nullptr; w->metaCap = 0;
-        if (hipMalloc((void**)&w->meta, metaBytes + 64u) != hipSuccess) rc = GC_ERR_NOMEM; else w->metaCap = metaBytes;
-    }
+    int rc = gc_buf_reserve(w->meta, metaBytes, 64u);
     if (rc == GC_OK && !w->ev0 && (hipEventCreate((hipEvent_t*)&w->ev0) != hipSuccess || hipEventCreate((hipEvent_t*)&w->ev1) != hipSuccess)) rc = GC_ERR_HIP;
     if (rc == GC_OK && hipMemcpyAsync(w->meta, host, metaBytes, hipMemcpyHostToDevice, st) != hipSuccess) rc = GC_ERR_HIP;
     if (rc == GC_OK) {

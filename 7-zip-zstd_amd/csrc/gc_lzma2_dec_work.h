@@ -1,10 +1,11 @@
-// gc_lzma2_dec_work.h -- the LZMA2 decoder's workspace, owned by a gc_ctx (gc_api.hip) and used by gc_lzma2_dec.h
+// gc_lzma2_dec_work.h -- the LZMA2 decoder's workspace, owned by a gc_ctx (gc_api.hip) and used by gc_lzma2_dec.h.  Include after the HIP runtime (or its emulator stand-in).
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
+#include "gc_devbuf.h"
 struct GcL2dWork {
-    uint8_t* meta; size_t metaCap;        // unit descriptors, their order, results, the two ticket counters
-    uint32_t instance;                    // test hook (GC_L2D_INSTANCE): 1 / 2 = every unit through the lc + lp <= 3 / the lc + lp <= 4 kernel instance; 0 = by the unit's flags
-    uint32_t nCU;                         // compute units of the device (the launch's width)
-    void* ev0; void* ev1; float ms;       // HIP events around the kernels of the last call
+    GcBuf<uint8_t> meta;                  // unit descriptors, their order, results, the two ticket counters
+    uint32_t instance = 0;                // test hook (GC_L2D_INSTANCE): 1 / 2 = every unit through the lc + lp <= 3 / the lc + lp <= 4 kernel instance; 0 = by the unit's flags
+    uint32_t nCU = 0;                     // compute units of the device (the launch's width)
+    void* ev0 = nullptr; void* ev1 = nullptr; float ms = 0.f;       // HIP events around the kernels of the last call
 };

@@ -1,10 +1,16 @@
 """CPU bring-up of the real kernel sources under the SIMT emulator (tests/emu): every stream must decode
 bit-exactly under the oracle decoder and the reference decoder.  Sizes are small: the emulator runs one
 workgroup at a time at roughly 1 s per 128 KiB block."""
+import importlib.util
+import os
+
 import numpy as np
 import pytest
 
 BLK = 128 * 1024
+_spec = importlib.util.spec_from_file_location("growth_cases", os.path.join(os.path.dirname(os.path.abspath(__file__)), "growth_cases.py"))
+G = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(G)
 
 
 def _roundtrip(O, enc, x):
@@ -63,6 +69,12 @@ def test_binary_alphabet_over_128_symbols(O, emu_enc):
 def test_deterministic(O, emu_enc):
     x = O.corpus("silesia-like", BLK)
     assert np.array_equal(emu_enc.code(x), emu_enc.code(x))
+
+
+@pytest.mark.parametrize("codec", ["flzma2", "zstd", "brotli"])
+def test_growing_the_workspace_never_changes_bytes(pkg, O, emu_lib_path, codec):
+    """small -> large -> small through ONE encoder: each stream equals a fresh encoder's (tests/growth_cases.py)"""
+    G.check_growth_keeps_bytes(pkg, O, codec, lib_path=emu_lib_path)
 
 
 def test_watchdog_word_turns_into_an_error_code(pkg, emu_lib_path, O, monkeypatch):

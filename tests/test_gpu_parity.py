@@ -7,11 +7,17 @@ Bit-exactness bars:
     (the encoder is deterministic by construction);
   * compressed size within a stated band of the reference encoder at the same level.
 """
+import importlib.util
+import os
+
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 BLK = 128 * 1024
+_spec = importlib.util.spec_from_file_location("growth_cases", os.path.join(os.path.dirname(os.path.abspath(__file__)), "growth_cases.py"))
+G = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(G)
 
 
 def _roundtrip(O, enc, x):
@@ -123,3 +129,24 @@ def test_dst_too_small_is_reported(O, gpu_enc, pkg):
     gpu_enc.code_device(d_src.data_ptr(), x.size, d_dst.data_ptr(), 1000)
     with pytest.raises(pkg.GpuCodecError):
         gpu_enc.finish()
+
+
+@pytest.mark.parametrize("codec", ["zstd", "flzma2", "brotli"])
+def test_growing_the_workspace_never_changes_bytes(pkg, O, gpu_enc, emu_lib_path, codec):
+    """small -> large -> small through ONE encoder of the product library: each stream equals a fresh encoder's (tests/growth_cases.py), the large one equals the
+    emulator's, and the zstd / brotli streams go back through ONE decoder on the same device in the same order, so that the decoders' workspaces grow as well."""
+    streams = G.check_growth_keeps_bytes(pkg, O, codec, device=0)
+    cls, level = getattr(pkg, G.CODECS[codec][0]), G.CODECS[codec][1]
+    emu = cls(level=level, lib_path=emu_lib_path)
+    try:
+        large = dict((k.split()[0], x) for k, x in G.inputs(O))["large"]
+        assert np.array_equal(streams["large"], emu.code(large)), codec
+    finally:
+        emu.close()
+    if codec != "flzma2":
+        dec = (pkg.ZstdDecoder if codec == "zstd" else pkg.BrotliDecoder)(device=0)
+        try:
+            for name, x in G.inputs(O):
+                assert np.array_equal(dec.code(streams[name.split()[0]]), x), (codec, name)
+        finally:
+            dec.close()
