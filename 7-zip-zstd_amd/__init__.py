@@ -33,7 +33,9 @@ EXPORTS = ["gc_test_hooks_enabled", "gc_lzfind_get_matches_device", "gc_device_c
            "gc_multi_piece_bytes", "gc_multi_compress_host",
            "gc_bra_convert_device", "gc_bra_x86_convert_device", "gc_delta_convert_device", "gc_zstd_scan_frames", "gc_zstd_scan_prefix", "gc_zstd_decompress_device", "gc_zstd_decompress_host", "gc_zstd_decompress_timing", "gc_zstd_decompress_kernel_timing", "gc_zstd_decompress_wide_rounds", "gc_zstd_decompress_selfcheck", "gc_filter_host",
            "gc_brotli_scan_prefix", "gc_brotli_dec_set_dictionary", "gc_brotli_dec_has_dictionary", "gc_brotli_decompress_device", "gc_brotli_decompress_host", "gc_brotli_decompress_timing",
-           "gc_lzma2_scan_prefix", "gc_lzma2_decompress_device", "gc_lzma2_decompress_host", "gc_lzma2_decompress_timing"]
+           "gc_lzma2_scan_prefix", "gc_lzma2_decompress_device", "gc_lzma2_decompress_host", "gc_lzma2_decompress_timing",
+           "gc_crc64_device", "gc_crc_segments_device", "gc_xz_compress_bound", "gc_xz_compress_device", "gc_xz_compress_host", "gc_xz_scan", "gc_xz_decompress_device", "gc_xz_decompress_host",
+           "gc_xz_timing", "gc_xz_launch_counts"]
 
 CODEC_ZSTD, CODEC_FLZMA2, CODEC_BROTLI = 0, 1, 2
 CODEC_IDS = {"zstd": CODEC_ZSTD, "flzma2": CODEC_FLZMA2, "brotli": CODEC_BROTLI}
@@ -167,6 +169,26 @@ def load_library(path=None):
     lib.gc_lzma2_decompress_host.restype = C.c_int
     lib.gc_lzma2_decompress_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     lib.gc_lzma2_decompress_timing.restype = C.c_int
+    lib.gc_crc64_device.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+    lib.gc_crc64_device.restype = C.c_int
+    lib.gc_crc_segments_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint64)]
+    lib.gc_crc_segments_device.restype = C.c_int
+    lib.gc_xz_compress_bound.argtypes = [C.c_size_t, C.c_size_t]
+    lib.gc_xz_compress_bound.restype = C.c_size_t
+    lib.gc_xz_compress_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]
+    lib.gc_xz_compress_device.restype = C.c_int
+    lib.gc_xz_compress_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]
+    lib.gc_xz_compress_host.restype = C.c_int
+    lib.gc_xz_scan.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
+    lib.gc_xz_scan.restype = C.c_int
+    lib.gc_xz_decompress_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.gc_xz_decompress_device.restype = C.c_int
+    lib.gc_xz_decompress_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.gc_xz_decompress_host.restype = C.c_int
+    lib.gc_xz_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    lib.gc_xz_timing.restype = C.c_int
+    lib.gc_xz_launch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint)]
+    lib.gc_xz_launch_counts.restype = C.c_int
     return lib
 
 
@@ -220,6 +242,29 @@ class BrotliChunk(C.Structure):
 class Lzma2Unit(C.Structure):
     """gc_lzma2_unit of include/gpucodec.h"""
     _fields_ = [("src_off", C.c_uint64), ("src_size", C.c_uint64), ("dst_off", C.c_uint64), ("dst_size", C.c_uint64), ("n_chunks", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class XzBlock(C.Structure):
+    """gc_xz_block of include/gpucodec.h"""
+    _fields_ = [("src_off", C.c_uint64), ("src_size", C.c_uint64), ("dst_off", C.c_uint64), ("dst_size", C.c_uint64), ("check_off", C.c_uint64),
+                ("check", C.c_uint32), ("dict_prop", C.c_uint32), ("first_unit", C.c_uint32), ("n_units", C.c_uint32)]
+
+
+class CrcSegment(C.Structure):
+    """gc_crc_segment of include/gpucodec.h"""
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint64)]
+
+
+XZ_CHECKS = {"none": 0, "crc32": 1, "crc64": 4}
+
+
+def crc64_device(ptr, n, lib_path=None):
+    """CRC-64/XZ (as C/XzCrc64.c) of n bytes at a device pointer (under the emulator: any host pointer), any alignment."""
+    v = C.c_uint64(0)
+    rc = load_library(lib_path).gc_crc64_device(ptr, n, C.byref(v))
+    if rc != GC_OK:
+        raise GpuCodecError("gc_crc64_device failed: %s" % _ERR.get(rc, rc))
+    return v.value
 
 
 def crc32_device(ptr, n, lib_path=None):
@@ -572,6 +617,96 @@ class Lzma2Decoder(_EncoderBase):
         ms = C.c_float(0)
         self._check(self._lib.gc_lzma2_decompress_timing(self._ctx, C.byref(ms)), "gc_lzma2_decompress_timing")
         return float(ms.value)
+
+
+class XzEncoder(_EncoderBase):
+    """The writer of bare .xz files (C/XzEnc.c XzEnc_Encode with a block size): the input in Blocks of `block_bytes` (0: the FLZMA2 piece size of the level), each an LZMA2
+    stream of the FLZMA2 encoder, the Blocks' checks ("none", "crc32", "crc64") from one launch of the segmented CRC kernel over the input."""
+
+    KERNELS = ("lzma2", "check")
+
+    def __init__(self, device=0, level=5, block_bytes=0, check="crc64", lib_path=None):
+        super().__init__(device, level, lib_path)
+        self.block_bytes = int(block_bytes)
+        self.check = XZ_CHECKS[check] if isinstance(check, str) else int(check)
+
+    def compress_bound(self, n):
+        return self._lib.gc_xz_compress_bound(n, self.block_bytes)
+
+    def code(self, data):
+        import numpy as np
+        a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+        cap = self.compress_bound(a.size)
+        out = np.empty(cap, dtype=np.uint8)
+        n = C.c_size_t(0)
+        self._check(self._lib.gc_xz_compress_host(self._ctx, a.ctypes.data, a.size, out.ctypes.data, cap, self.level, self.block_bytes, self.check, C.byref(n)), "gc_xz_compress_host")
+        return out[:n.value]
+
+    def code_device(self, d_src_ptr, n, d_dst_ptr, dst_cap):
+        """-> the stream's size (the call waits for it: a Block's place depends on the size of the one in front of it)"""
+        size = C.c_size_t(0)
+        self._check(self._lib.gc_xz_compress_device(self._ctx, d_src_ptr, n, d_dst_ptr, dst_cap, self.level, self.block_bytes, self.check, C.byref(size)), "gc_xz_compress_device")
+        return size.value
+
+    def segment_checks(self, d_ptr, segments, check="crc64"):
+        """gc_crc_segments_device: the checks of many (offset, length) segments of one device buffer from one launch, on this context's stream"""
+        segs = (CrcSegment * max(1, len(segments)))(*[CrcSegment(int(o), int(l)) for o, l in segments])
+        out = (C.c_uint64 * max(1, len(segments)))()
+        self._check(self._lib.gc_crc_segments_device(self._ctx, d_ptr, segs, len(segments), XZ_CHECKS[check] if isinstance(check, str) else int(check), out), "gc_crc_segments_device")
+        return [int(v) for v in out[:len(segments)]]
+
+    def last_timing_ms(self):
+        ms = (C.c_float * 2)()
+        self._check(self._lib.gc_xz_timing(self._ctx, ms), "gc_xz_timing")
+        return dict(zip(self.KERNELS, [float(x) for x in ms]))
+
+
+class XzDecoder(_EncoderBase):
+    """The reader of bare .xz files (C/XzIn.c, C/XzDec.c) for whole files: the container is scanned on the host from its end, the units of ALL Blocks decode side by side
+    in one LZMA2 launch set, and one launch of the segmented CRC kernel checks every Block's content."""
+
+    KERNELS = ("lzma2", "check")
+
+    def scan(self, data):
+        """-> (array of XzBlock, their number, array of Lzma2Unit (all Blocks', offsets relative to the whole file and the whole output), their number, the sum of the contents)"""
+        import numpy as np
+        a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+        nb = C.c_size_t(0); nu = C.c_size_t(0); total = C.c_uint64(0)
+        rc = self._lib.gc_xz_scan(a.ctypes.data, a.size, None, 0, C.byref(nb), None, 0, C.byref(nu), C.byref(total))
+        if rc != GC_OK:
+            raise GpuCodecError("gc_xz_scan failed: %s" % _ERR.get(rc, rc))
+        blocks = (XzBlock * max(1, nb.value))(); units = (Lzma2Unit * max(1, nu.value))()
+        rc = self._lib.gc_xz_scan(a.ctypes.data, a.size, blocks, nb.value, C.byref(nb), units, nu.value, C.byref(nu), C.byref(total))
+        if rc != GC_OK:
+            raise GpuCodecError("gc_xz_scan failed: %s" % _ERR.get(rc, rc))
+        return blocks, nb.value, units, nu.value, total.value
+
+    def code(self, data, capacity=None):
+        """.xz file -> numpy uint8 content (host buffers; includes PCIe copies).  capacity: the scan's exact total unless given."""
+        import numpy as np
+        a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+        if capacity is None:
+            capacity = self.scan(a)[4]
+        out = np.empty(max(1, capacity), dtype=np.uint8)
+        n = C.c_size_t(0)
+        self._check(self._lib.gc_xz_decompress_host(self._ctx, a.ctypes.data, a.size, out.ctypes.data, capacity, C.byref(n)), "gc_xz_decompress_host")
+        return out[:n.value]
+
+    def code_device(self, d_src_ptr, n, d_dst_ptr, dst_cap, blocks, n_blocks, units, n_units):
+        size = C.c_size_t(0)
+        self._check(self._lib.gc_xz_decompress_device(self._ctx, d_src_ptr, n, d_dst_ptr, dst_cap, blocks, n_blocks, units, n_units, C.byref(size)), "gc_xz_decompress_device")
+        return size.value
+
+    def last_timing_ms(self):
+        ms = (C.c_float * 2)()
+        self._check(self._lib.gc_xz_timing(self._ctx, ms), "gc_xz_timing")
+        return dict(zip(self.KERNELS, [float(x) for x in ms]))
+
+    def launch_counts(self):
+        """of the last decode: (LZMA2 decode launch sets, units in them, launches of the check kernel)"""
+        v = (C.c_uint * 3)()
+        self._check(self._lib.gc_xz_launch_counts(self._ctx, v), "gc_xz_launch_counts")
+        return int(v[0]), int(v[1]), int(v[2])
 
 
 class ZstdDecoder(_EncoderBase):

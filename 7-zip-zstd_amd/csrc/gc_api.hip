@@ -151,6 +151,8 @@ struct gc_ctx {
     uint64_t* hostResult = nullptr;     // pinned
     GcBrDecWork brd;          // BROTLI decoder (gc_brotli_dec.hip)
     GcL2dWork l2d;            // LZMA2 decoder (gc_lzma2_dec.h)
+    // .xz container (gc_xz.h): the stored Checks of a file in device memory (offsets in, values out); events around the check kernel; figures of the last gc_xz_* call
+    GcBuf<uint64_t> xzWork; hipEvent_t xzEv[2] = {}; float xzMs[2] = {}; unsigned xzCounts[3] = {};      // ms: LZMA2 kernels, check kernel; counts: decode launch sets, units, check launches
     // staging for the host-buffer entry points (stage_reserve)
     GcBuf<uint8_t> dIn, dOut, dPre;      // (dPre: the pre-filtered input of gc_host_begin_pre)
     bool pending = false; bool timed = false;
@@ -261,6 +263,7 @@ static void ctx_release(gc_ctx* c)
         for (uint32_t i = 0; i < GC_PART_EVENTS; i++) if (c->evPart[p][i]) hipEventDestroy(c->evPart[p][i]);
     }
     for (int i = 0; i < 2; i++) if (c->evHash[i]) hipEventDestroy(c->evHash[i]);
+    for (int i = 0; i < 2; i++) if (c->xzEv[i]) hipEventDestroy(c->xzEv[i]);
     if (c->streamHash) hipStreamDestroy(c->streamHash);
     if (c->stream3) hipStreamDestroy(c->stream3);
     if (c->stream2) hipStreamDestroy(c->stream2);
@@ -1745,3 +1748,6 @@ extern "C" int gc_lzma2_decompress_host(gc_ctx* c, const void* src, size_t n, vo
     return rc;
 }
 extern "C" int gc_lzma2_decompress_timing(gc_ctx* c, float* ms) { if (!c || !ms) return GC_ERR_PARAM; *ms = c->l2d.ms; return GC_OK; }
+
+// ---- the .xz container: reader, writer and their entry points
+#include "gc_xz.h"

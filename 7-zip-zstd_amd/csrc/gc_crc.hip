@@ -131,3 +131,5 @@ extern "C" int gc_crc32_device(const void* d_src, size_t n, uint32_t* crc)
     *crc = reg ^ init ^ 0xFFFFFFFFu;
     return GC_OK;
 }
+
+#include "gc_crc_seg.h"      // the segmented CRC-64 / CRC-32 kernels of the .xz container and gc_crc64_device

@@ -357,6 +357,62 @@ int         gc_lzma2_decompress_host(gc_ctx* ctx, const void* src, size_t n, voi
 /* HIP-event duration of the decode kernels of the last gc_lzma2_decompress_* call */
 int         gc_lzma2_decompress_timing(gc_ctx* ctx, float* ms);
 
+/* ---- CRC-64 of data that lies in device memory (C/XzCrc64.c Crc64Calc: CRC-64/XZ, reflected polynomial 0xC96C5795D7870F42, init and final XOR all ones;
+ * "123456789" gives 0x995DC9BBDF1939FA): the Check of an .xz block.  Any alignment of d_src.  Synchronous, on the current device's default stream. */
+int         gc_crc64_device(const void* d_src, size_t n, uint64_t* crc);
+/* The checks of MANY segments of one device buffer from ONE kernel launch, on the context's stream: out[i] (host memory) = the check of the bytes
+ * [segs[i].offset, segs[i].offset + segs[i].length) of d_src; any offset, any length, 0 included; segments may overlap.  check: GC_XZ_CHECK_CRC32 (the value of
+ * gc_crc32_device, in the low 32 bits) or GC_XZ_CHECK_CRC64.  This is what the .xz entry points below compute their blocks' Check fields with. */
+typedef struct gc_crc_segment { uint64_t offset, length; } gc_crc_segment;
+int         gc_crc_segments_device(gc_ctx* ctx, const void* d_src, const gc_crc_segment* segs, size_t nSegs, int check, uint64_t* out);
+
+/* ---- The .xz container around LZMA2 (the third bare-file format; C/Xz.h, C/XzEnc.c, C/XzDec.c, C/XzIn.c, C/XzCrc64.c; "The .xz File Format" 1.0.4).
+ * A stream is: Stream Header | Blocks | Index | Stream Footer.  Every Block is an LZMA2 stream of its own (dictionary reset at its start, end marker at its end) behind a
+ * Block Header and in front of its Check, and the Index lists every Block's packed and unpacked size -- so the Blocks of a file are found without walking payloads and
+ * decode side by side: the units of all Blocks go through ONE gc_lzma2_decompress_device launch set, their Checks through ONE launch of the segmented CRC kernel.
+ *   gc_xz_compress_device   <->  XzEnc_Encode (C/XzEnc.c) with blockSize = blockBytes: the input is cut into Blocks of blockBytes (0: gc_multi_piece_bytes(GC_CODEC_FLZMA2, level);
+ *                                below 4096: GC_ERR_PARAM), each coded by gc_flzma2_compress_device at `level`; Block Headers state both sizes and the one filter 0x21 with
+ *                                gc_flzma2_dict_prop(level).  check: GC_XZ_CHECK_NONE / _CRC32 / _CRC64 (others: GC_ERR_PARAM); the Checks of all Blocks come from one launch
+ *                                over d_src.  Synchronous (a Block's place depends on the size of the one in front of it): returns the size itself, there is no finish.
+ *                                n == 0 gives the 32-byte stream with an empty Index.
+ *   gc_xz_compress_host     H2D (once) + the above + D2H.
+ *   gc_xz_compress_bound    worst case of the above for n bytes in Blocks of blockBytes (0: as above, at the level whose blocks are smallest).
+ *   gc_xz_scan              <->  Xzs_ReadBackward (C/XzIn.c): host; from the end of the file: Stream Footer -> Index -> Blocks, stream after stream towards offset 0 (concatenated
+ *                                streams, Stream Padding = zero bytes in a multiple of four between and behind them).  Verifies every header CRC-32, the Index against the Block Headers
+ *                                (where those state sizes), the footer's flags against the header's, and walks every payload's chunk headers with gc_lzma2_scan_prefix: whole units,
+ *                                the end marker reached, the payload consumed exactly, the units' sizes summing to the Index's.  blocks / units may be NULL to count.  units: all
+ *                                Blocks' units in file order, src_off relative to the whole file, dst_off to the whole output.
+ *                                GC_ERR_UNSUPPORTED (never bytes passed through): a filter chain other than LZMA2 alone (BCJ / Delta in front of it), a Check other than
+ *                                none / CRC-32 / CRC-64 (SHA-256 and the reserved ids).  GC_ERR_CORRUPT: every structural violation or CRC mismatch.
+ *   gc_xz_decompress_device blocks and units as the scan returned them (host memory), d_src / d_dst device memory.  Streams of different dictionary sizes are decoded with the
+ *                                largest property byte.  GC_ERR_CORRUPT: a damaged payload, or a stored Check that is not the decoded content's.
+ *   gc_xz_decompress_host   scan + H2D + decode + D2H (the stored Checks are read from the host copy).
+ *   gc_xz_timing            last gc_xz_* call of the context: ms[0] the LZMA2 kernels (encoder: summed over the Blocks), ms[1] the check kernel
+ *   gc_xz_launch_counts     last gc_xz_decompress_* call: n[0] LZMA2 decode launch sets, n[1] units in them, n[2] launches of the check kernel */
+#define GC_XZ_CHECK_NONE  0
+#define GC_XZ_CHECK_CRC32 1
+#define GC_XZ_CHECK_CRC64 4
+typedef struct gc_xz_block {
+    uint64_t src_off, src_size;      /* the Block's LZMA2 stream (its end marker included) inside the file */
+    uint64_t dst_off, dst_size;      /* where its content goes in the output, and how much it is */
+    uint64_t check_off;              /* the stored Check inside the file (0, 4 or 8 bytes by `check`) */
+    uint32_t check;                  /* GC_XZ_CHECK_* of the Block's stream */
+    uint32_t dict_prop;              /* the LZMA2 filter's property byte */
+    uint32_t first_unit, n_units;    /* the Block's units in the scan's unit list */
+} gc_xz_block;
+size_t      gc_xz_compress_bound(size_t n, size_t blockBytes);
+int         gc_xz_compress_device(gc_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t dstCapacity, int level, size_t blockBytes, int check,
+                                  size_t* compressedSize);
+int         gc_xz_compress_host(gc_ctx* ctx, const void* src, size_t n, void* dst, size_t dstCapacity, int level, size_t blockBytes, int check,
+                                size_t* compressedSize);
+int         gc_xz_scan(const void* src, size_t n, gc_xz_block* blocks, size_t maxBlocks, size_t* nBlocks, gc_lzma2_unit* units, size_t maxUnits, size_t* nUnits,
+                       uint64_t* contentTotal);
+int         gc_xz_decompress_device(gc_ctx* ctx, const void* d_src, size_t n, void* d_dst, size_t dstCapacity, const gc_xz_block* blocks, size_t nBlocks,
+                                    const gc_lzma2_unit* units, size_t nUnits, size_t* decompressedSize);
+int         gc_xz_decompress_host(gc_ctx* ctx, const void* src, size_t n, void* dst, size_t dstCapacity, size_t* decompressedSize);
+int         gc_xz_timing(gc_ctx* ctx, float ms[2]);
+int         gc_xz_launch_counts(gc_ctx* ctx, unsigned n[3]);
+
 /* raw stream handle (hipStream_t) so callers can order their own work against the context */
 void*       gc_ctx_stream(gc_ctx* ctx);
 
