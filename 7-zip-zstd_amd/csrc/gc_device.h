@@ -77,6 +77,15 @@ __device__ __forceinline__ void gc_wave_sync_global()
 #endif
 }
 
+// Keeps the compiler's scheduler from moving instructions across this point.  An unrolled loop of independent latency chains is otherwise interleaved
+// as far as the registers go, and beyond: this bounds how many chains are in flight together.
+__device__ __forceinline__ void gc_sched_fence()
+{
+#ifndef HIPEMU
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+}
+
 // Kernels that run beside each other: the producer makes what it wrote visible to the whole device and counts itself in; the consumer polls the
 // counter and, once it has seen the value it waits for, drops what its caches may hold of the producer's lines (agent scope: across the XCDs' L2s).
 __device__ __forceinline__ void gc_signal_device(uint32_t* counter)         // called by every lane of the wave; one lane counts

@@ -1071,7 +1071,8 @@ __device__ __forceinline__ uint32_t pz_exit(uint32_t nxt)
 // The levels that parse the first pass's records as they are (no far pass, no link following, no price-based parse) never need the
 // records in HBM: a tile is verified into LDS (mf_verify_tile) and parsed right there (rounds 2-3 had one workgroup per BLOCK take the block's
 // tiles in order; since round 3 every tile has a workgroup of its own, below).  The parse of a tile is W6's scheme at tile scale -- every wave composes the exit maps of its 16 segments, the maps
-// are chained from the lane at which the path entered the tile, every wave walks its segments from its real entry -- and because the
+// are chained from the lane at which the path entered the tile, every wave hops through the maps it kept to the real entry of each of its segments and
+// walks the 16 of them at the same time, one lane per segment -- and because the
 // tiles are taken in order the entry lane, the sequence count and the literal count simply carry over from tile to tile: no group
 // maps, no second reading of the records.  Literal bytes come from the staged tile.  The lazy look-ahead stops at the tile's end
 // (the records of the next tile do not exist yet): a position in the last two bytes of a tile takes its match as it is.
@@ -1107,7 +1108,8 @@ MFK(gc_mf_vparse_tile_kernel)(const uint8_t* __restrict__ src, uint64_t srcSize,
     __shared__ uint32_t sW[MFV_STAGE_WORDS];
     __shared__ uint32_t sRec[GC_MF_TILE];
     __shared__ uint8_t sExt[4u];
-    __shared__ uint32_t sAux[GC_MF_TILE / 4u];                    // verify: the tile's run table; parse: take << 7 | next position, one byte per position
+    __shared__ uint32_t sAux[GC_MF_TILE / 4u];                    // verify: the tile's run table; parse: next position within the segment (1 .. 127), one byte per position
+    static_assert(VP_SPW % 4u == 0u && VP_SPW <= 64u, "the parse keeps a wave's exit maps four to a register and walks one segment per lane");
     uint32_t* sStart = sAux; uint32_t* sLocal = sAux + GC_MF_PARTS; uint32_t* sWaveTot = sAux + 2u * GC_MF_PARTS + 1u;
     uint8_t* sNxt = (uint8_t*)sAux;
     __shared__ uint8_t  sExitW[VP_WAVES][64];
@@ -1129,47 +1131,68 @@ MFK(gc_mf_vparse_tile_kernel)(const uint8_t* __restrict__ src, uint64_t srcSize,
     mf_verify_tile<MF_BASE, true>(T, src, srcSize, frameBlocks, offs, ent, nullptr, sW, sRec, sExt, sStart, sLocal, sWaveTot, prof, &tprev);
     const uint32_t n = T.len;
     VP_PHASE(prof, tprev, 2);
-    // ---- exit map of this wave's segments
+    // ---- exit map of this wave's segments.  The maps stay in registers (x4, lane = entry lane): the loop has no branch, so the six ds_bpermute rounds of
+    //      different segments are in flight together and only the composition across the groups of four is a chain.  A segment past the tile's end has records of 0 everywhere
+    //      (pz_seg): whatever its map says, nothing enters it that counts.
     const uint32_t seg0 = wave * VP_SPW;
+    uint32_t x4[VP_SPW / 4u];                                     // exit maps, four segments to a register (a byte each)
     {
         uint32_t comp = lane;
-#pragma unroll 1
-        for (uint32_t k = 0; k < VP_SPW; k++) {
-            const uint32_t seg = seg0 + k;
-            if (seg * 64u >= n) break;                            // (uniform) past the end: the identity
-            const PzSeg s = pz_seg(sRec, seg * 64u + lane, n, lane, lazy);
-            sNxt[seg * 64u + lane] = (uint8_t)(s.nxt | (s.take ? 0x80u : 0u));
-            const uint32_t ex = pz_exit(s.nxt) - 64u;
-            comp = __shfl(ex, (int)comp);
+#pragma unroll
+        for (uint32_t g = 0; g < VP_SPW / 4u; g++) {
+            uint32_t m[4];
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; j++) {
+                const uint32_t k = 4u * g + j, seg = seg0 + k;
+                const PzSeg s = pz_seg(sRec, seg * 64u + lane, n, lane, lazy);
+                sNxt[seg * 64u + lane] = (uint8_t)s.nxt;
+                m[j] = pz_exit(s.nxt) - 64u;
+                const uint64_t tk = __ballot(s.take);
+                if (lane == 0) sMaskSeq[seg] = tk;               // parked for the lane that walks the segment
+            }
+            x4[g] = m[0] | (m[1] << 8) | (m[2] << 16) | (m[3] << 24);
+            // the wave's map = the maps composed in order (a then b: b[a[lane]]); the four of a group as a tree
+            m[0] = __shfl(m[1], (int)m[0]); m[2] = __shfl(m[3], (int)m[2]); m[0] = __shfl(m[2], (int)m[0]);
+            comp = __shfl(m[0], (int)comp);
+            gc_sched_fence();                                    // (four chains in flight, not sixteen: the kernel has 80 VGPRs)
         }
         sExitW[wave][lane] = (uint8_t)comp;
     }
     __syncthreads();
-    VP_PHASE(prof, tprev, 3);
-    // ---- real entry lane of this wave: lane 0 of the tile chained through the waves in front
+    VP_PHASE(prof, tprev, 3);                                      // exit maps
+    // ---- real entry lane of this wave: lane 0 of the tile chained through the waves in front; the entry lane of each of its segments: one hop through the
+    //      segment's exit map (lane k keeps segment k's)
     uint32_t e = 0;
     for (uint32_t w = 0; w < wave; w++) e = sExitW[w][e];
     e = gc_uniform(e);
-    VP_PHASE(prof, tprev, 4);
-    // ---- walk the segments from the real entry: path masks + counts
-    uint32_t nS = 0, nL = 0;
-#pragma unroll 1
+    uint32_t myE = 0;
+#pragma unroll
     for (uint32_t k = 0; k < VP_SPW; k++) {
-        const uint32_t seg = seg0 + k;
-        if (seg * 64u >= n) break;
-        const uint32_t p = seg * 64u + lane;
-        const uint32_t nb = sNxt[p], nxt = nb & 0x7Fu;
-        uint64_t path = 0;
-        uint32_t c = e;
-        while (c < 64u) { path |= 1ull << c; c = gc_readlane(nxt, c); }
-        e = c - 64u;
-        const uint64_t takeMask = __ballot((nb & 0x80u) != 0u), inMask = __ballot(p < n);
-        const uint64_t mS = path & takeMask, mL = path & ~takeMask & inMask;
-        if (lane == 0) { sMaskSeq[seg] = mS; sMaskLit[seg] = mL; }
-        nS += (uint32_t)__popcll(mS); nL += (uint32_t)__popcll(mL);
+        myE = gc_writelane(myE, e, k);
+        e = (gc_readlane(x4[k >> 2], e) >> (8u * (k & 3u))) & 0xFFu;
     }
-    if (lane == 0) { sCntSeq[wave] = nS; sCntLit[wave] = nL; }
+    // ---- walk the segments from their real entries, all at the same time: lane k follows segment k (one byte of sNxt per hop) -> path masks + counts.
+    //      Bounded: nxt > lane (a record is 0 or >= GC_MIN_MATCH, a literal steps by 1), and the loop has a cap of its own.
+    uint32_t cnt = 0;
+    {
+        const uint32_t seg = seg0 + lane;
+        const bool mine = lane < VP_SPW && seg * 64u < n;
+        const uint32_t lim = mine ? (n - seg * 64u < 64u ? n - seg * 64u : 64u) : 0u;       // the path stops at the segment's or the tile's end
+        const uint8_t* row = sNxt + (mine ? seg * 64u : 0u);
+        uint64_t path = 0;
+        uint32_t c = myE;
+        for (uint32_t i = 0; i < 64u && c < lim; i++) { path |= 1ull << c; c = row[c]; }
+        if (mine) {
+            const uint64_t myTake = sMaskSeq[seg];
+            const uint64_t mS = path & myTake, mL = path & ~myTake;                          // (every bit of path is a position of the tile: c < lim)
+            sMaskSeq[seg] = mS; sMaskLit[seg] = mL;
+            cnt = ((uint32_t)__popcll(mS) << 16) | (uint32_t)__popcll(mL);                   // (a wave has 1024 positions: 16 bits each)
+        }
+    }
+    cnt = gc_wave_sum(cnt);
+    if (lane == 0) { sCntSeq[wave] = cnt >> 16; sCntLit[wave] = cnt & 0xFFFFu; }
     __syncthreads();
+    VP_PHASE(prof, tprev, 4);                                      // entry lanes + walk, up to the barrier (slot 5 is what follows: counts out + poll)
     uint32_t sBefore = 0, lBefore = 0, sAll = 0, lAll = 0;
     for (uint32_t w = 0; w < VP_WAVES; w++) {
         const uint32_t cs = sCntSeq[w], cl = sCntLit[w];

@@ -44,7 +44,12 @@ else:
     enc.set_phase_profile(True)
     run(); ph = enc.phase_profile(); tp = enc.last_timing_ms()
     enc.set_phase_profile(False)
+# what the seven lz.* slots hold when the fused verify + parse kernel ran (zstd levels 1-4; VP_PHASE in gc_lz_window.hip): thread 0's clock per tile
+FUSED_SLOTS = {"lz.probe": "stage + run offsets", "lz.insert": "listed positions", "lz.verify": "unlisted positions + continuation", "lz.double": "exit maps (to the barrier)",
+               "lz.chain": "entry lanes + walk (to the barrier)", "lz.walk": "counts out + poll for the tiles in front", "lz.emit": "emit"}
+fused = not fl2 and not br and enc.level <= 4
 print(json.dumps({"codec": a.codec, "level": enc.level, "corpus": a.corpus, "bytes": a.bytes, "compressed": size, "ratio": round(a.bytes / size, 4),
                   "GBps_total": round(a.bytes / acc["total"] / 1e6, 2), "kernel_ms": {k: round(v, 4) for k, v in acc.items()},
                   "kernel_ms_profiled": {k: round(v, 4) for k, v in tp.items()},
-                  "phase_cycles_per_block": {k: round(v) for k, v in ph.items()}}))
+                  "phase_cycles_per_block": {k: round(v) for k, v in ph.items()},
+                  "fused_kernel_phases": {FUSED_SLOTS[k]: round(v) for k, v in ph.items() if k in FUSED_SLOTS} if fused else None}))
