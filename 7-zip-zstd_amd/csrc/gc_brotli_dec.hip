@@ -192,7 +192,7 @@ __device__ __forceinline__ uint32_t brd_alloc(BrdArena& a, uint32_t bytes)      
     if (a.m.hbm && a.hbmUsed + bytes <= a.hbmCap) { const uint32_t h = a.hbmUsed | BRD_H_HBM; a.hbmUsed += bytes; return h; }
     return ~0u;
 }
-__device__ __forceinline__ uint32_t brd_alloc_lds(BrdArena& a, uint32_t bytes)  // maps, modes, directories: read per symbol, so LDS or nothing
+__device__ __forceinline__ uint32_t brd_alloc_lds(BrdArena& a, uint32_t bytes)  // modes, directories: read per symbol, so LDS or nothing (the context maps too where they fit: brd_alloc)
 {
     bytes = (bytes + 7u) & ~7u;
     if (a.ldsUsed + bytes <= a.ldsCap) { const uint32_t h = a.ldsUsed; a.ldsUsed += bytes; return h; }
@@ -555,10 +555,10 @@ __device__ __forceinline__ void brd_kernel_body(const uint8_t* __restrict__ src,
                                 M.nTrees[0] = 1; M.nTrees[1] = M.nTypes[1]; M.nTrees[2] = 1;
                                 if (st == BRD_OK) {
                                     const uint32_t sl = 64u * M.nTypes[0], sd = 4u * M.nTypes[2];
-                                    M.cmapL = brd_alloc_lds(A, sl + sd); M.cmapD = M.cmapL + sl;
+                                    M.cmapL = brd_alloc(A, sl + sd); M.cmapD = M.cmapL + sl;      // (256 literal block types are 16 KiB of map: more than the smallest instance's arena, so the page takes it then)
                                     if (M.cmapL == ~0u) st = BRD_LIMIT;
-                                    if (st == BRD_OK) brd_context_map(b, sl, M.nTrees[0], sArena + M.cmapL, A, &sScratch, st);
-                                    if (st == BRD_OK) brd_context_map(b, sd, M.nTrees[2], sArena + M.cmapD, A, &sScratch, st);
+                                    if (st == BRD_OK) brd_context_map(b, sl, M.nTrees[0], (uint8_t*)brd_at(A.m, M.cmapL), A, &sScratch, st);
+                                    if (st == BRD_OK) brd_context_map(b, sd, M.nTrees[2], (uint8_t*)brd_at(A.m, M.cmapL) + sl, A, &sScratch, st);
                                 }
                                 if (st == BRD_OK) {
                                     const uint32_t d0 = brd_alloc_lds(A, (M.nTrees[0] + M.nTrees[1] + M.nTrees[2]) * 4u);
@@ -629,19 +629,23 @@ __device__ __forceinline__ void brd_kernel_body(const uint8_t* __restrict__ src,
             // ---- context tables: the literal's tree from the last byte and the class of the byte before it in ONE read (context id, then context map, are two)
             const uint32_t nCtxTab = gc_uniform(sMeta.nCtxTab), nTreesL = gc_uniform(sMeta.nTrees[0]), nTreesD = gc_uniform(sMeta.nTrees[2]);
             uint8_t* const ctxTab = sArena + sMeta.ctxTab;
+            // the context maps: in the arena, or in the page where the arena did not take them (an offset and a flag, so that the arena is still read as LDS)
+            const bool mapInPage = (gc_uniform(sMeta.cmapL) & BRD_H_HBM) != 0u;
+            const uint32_t cmapL = gc_uniform(sMeta.cmapL) & BRD_H_OFF, cmapD = gc_uniform(sMeta.cmapD) & BRD_H_OFF;
+            #define BRD_MAP(at) (mapInPage ? mem.hbm[at] : sArena[at])
             for (uint32_t t = 0; t < nCtxTab; t++) {
-                const uint32_t md = (sArena + sMeta.modes)[t]; const uint8_t* row = sArena + sMeta.cmapL + 64u * t;
+                const uint32_t md = (sArena + sMeta.modes)[t]; const uint32_t row = cmapL + 64u * t;
                 for (uint32_t e = lane; e < 2048u; e += 64u) {
                     const uint32_t a = e >> 3, j = e & 7u;
                     const uint32_t ctx = md == 2u ? (sLut[a] | (j & 3u)) : (md == 0u ? (a & 63u) : (md == 1u ? a >> 2 : ((brd_signed(a) << 3) | j)));
-                    ctxTab[2048u * t + e] = row[ctx];
+                    ctxTab[2048u * t + e] = BRD_MAP(row + ctx);
                 }
             }
             // ---- commands: every lane runs the same state machine
             BrdBlocks BL[3];
             for (uint32_t k = 0; k < 3u; k++) { BL[k].n = gc_uniform(sMeta.nTypes[k]); BL[k].type = 0; BL[k].prev = 1; BL[k].left = gc_uniform(sMeta.left[k]); BL[k].typeCode = gc_uniform(sMeta.typeCode[k]); BL[k].countCode = gc_uniform(sMeta.countCode[k]); }
             const uint32_t npostfix = gc_uniform(sMeta.npostfix), ndirect = gc_uniform(sMeta.ndirect);
-            const uint8_t* const cmapL = sArena + sMeta.cmapL; const uint8_t* const cmapD = sArena + sMeta.cmapD; const uint8_t* const modes = sArena + sMeta.modes;
+            const uint8_t* const modes = sArena + sMeta.modes;
             gc_wave_sync();                                       // (sMeta is lane 0's to write again from here; the tables are whole)
             BRD_T(1)
             BRD_S(0, hb)
@@ -650,7 +654,7 @@ __device__ __forceinline__ void brd_kernel_body(const uint8_t* __restrict__ src,
 #endif
             const uint32_t mEnd = pos + mlen;
             uint32_t mode = gc_uniform(modes[0]);
-            const uint8_t* cmRow = cmapL;
+            uint32_t cmRow = cmapL;
             const uint8_t* ctRow = ctxTab;
             // class of a byte as the byte BEFORE the last one (UTF8: 2 bits, SIGNED: 3 bits, the other modes do not look at it)
             #define BRD_CLASS(x) (mode == 2u ? (uint32_t)sLut[256u + (x)] : (mode == 3u ? brd_signed(x) : 0u))
@@ -706,7 +710,7 @@ __device__ __forceinline__ void brd_kernel_body(const uint8_t* __restrict__ src,
                         else if (mode == 0u) ctx = p1 & 63u;
                         else if (mode == 1u) ctx = p1 >> 2;
                         else ctx = (brd_signed(p1) << 3) | brd_signed(p2);
-                        tl = gc_uniform(cmRow[ctx]);
+                        tl = gc_uniform(BRD_MAP(cmRow + ctx));
                     }
                     const uint32_t lit = brd_sym_t<8>(hb, tabL, nTabL, dirL, tl, mem, lane);
                     if (pos - flushed >= RING - 64u) { gc_wave_sync(); brd_flush<RING>(sRing, out, flushed, pos, lane); flushed = pos; unfenced = true; gc_wave_sync(); }
@@ -724,7 +728,7 @@ __device__ __forceinline__ void brd_kernel_body(const uint8_t* __restrict__ src,
                     if (BL[2].left == 0u) brd_switch_w(hb, BL[2], mem, K, lane);
                     BL[2].left--;
                     const uint32_t dctx = cplen > 4u ? 3u : cplen - 2u;
-                    const uint32_t td = nTreesD > 1u ? gc_uniform(cmapD[4u * BL[2].type + dctx]) : 0u;
+                    const uint32_t td = nTreesD > 1u ? gc_uniform(BRD_MAP(cmapD + 4u * BL[2].type + dctx)) : 0u;
                     dcode = brd_sym_t<8>(hb, tabD, nTabD, dirD, td, mem, lane);
                 }
                 const uint32_t maxDist = pos < maxBack ? pos : maxBack;
@@ -828,6 +832,7 @@ __device__ __forceinline__ void brd_kernel_body(const uint8_t* __restrict__ src,
                 BRD_T(5)
             }
             #undef BRD_CLASS
+            #undef BRD_MAP
             b = hb;
             if (b.over && status == BRD_OK) status = BRD_CORRUPT;
             gc_wave_sync_global();
@@ -1008,8 +1013,9 @@ int gc_brd_decode(hipStream_t st, GcBrDecWork* w, const uint8_t* d_src, const gc
     switch (tot[1]) {
         case 0: *produced = (size_t)tot[0]; return GC_OK;
         case BRD_DST_SMALL + 16u: if (err) snprintf(err, errCap, "destination too small: need %llu bytes", (unsigned long long)tot[0]); return GC_ERR_DST_SMALL;
+        case BRD_DST_SMALL: if (err) snprintf(err, errCap, "a brotli stream's meta-block outgrows the capacity of its chunk (the frame's hint, or the destination of a bare stream)"); return GC_ERR_DST_SMALL;
         case BRD_DICTIONARY: if (err) snprintf(err, errCap, "the brotli stream refers to the static dictionary of RFC 7932 and the host has not handed it over (gc_brotli_dec_set_dictionary)"); return GC_ERR_UNSUPPORTED;
         case BRD_LIMIT: if (err) snprintf(err, errCap, "a meta-block of the brotli stream holds more prefix codes than this decoder's arenas take"); return GC_ERR_UNSUPPORTED;
-        default: if (err) snprintf(err, errCap, "damaged brotli stream (chunk status %u)", (unsigned)tot[1]); return GC_ERR_CORRUPT;   // (a chunk that outgrows its brotli-mt hint is one, brotli-mt_decompress.c:243)
+        default: if (err) snprintf(err, errCap, "damaged brotli stream (chunk status %u)", (unsigned)tot[1]); return GC_ERR_CORRUPT;
     }
 }
