@@ -390,7 +390,7 @@ gc_zstd_dec_index_kernel(const uint8_t* __restrict__ src, const GcZdFrame* __res
                                 if (sf < 2u) { regen = (uint32_t)(v >> 4) & 0x3FFu; comp = (uint32_t)(v >> 14) & 0x3FFu; nStreams = sf == 0u ? 1u : 4u; }
                                 else if (sf == 2u) { regen = (uint32_t)(v >> 4) & 0x3FFFu; comp = (uint32_t)(v >> 18) & 0x3FFFu; nStreams = 4; }
                                 else { regen = (uint32_t)(v >> 4) & 0x3FFFFu; comp = (uint32_t)(v >> 22) & 0x3FFFFu; nStreams = 4; }
-                                if (regen == 0u) bad = true;
+                                // (one stream may regenerate 0 bytes -- its payload is a tree and an end mark; four streams regenerate at least 6: the literals kernel)
                             }
                         }
                         if (regen > GC_ZSTD_BLOCK_MAX || (uint64_t)hdr + comp >= bs) bad = true;       // at least the sequence count follows
@@ -1039,7 +1039,7 @@ gc_zstd_dec_exec_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, uint8
             uint32_t fail = 0;
             if (e.type & GC_ZD_B_BAD) fail = GC_ZD_CORRUPT;
             else if (bt == 2u && (e.status || e.litStatus)) fail = e.status ? e.status : e.litStatus;
-            else if (produced + (bt == 2u ? e.outSize : e.regen) > cap) fail = GC_ZD_DST_SMALL;
+            else if (produced + (bt == 2u ? e.outSize : e.regen) > cap) fail = (fr.flags & GC_ZD_F_SIZE_KNOWN) ? GC_ZD_SIZE : GC_ZD_DST_SMALL;      // more than the frame says it holds is damage, whatever the room
             if (fail) { if (t == 0) sV[XV_ERR] = fail; break; }
             const uint8_t* const bsrc = src + e.srcOff;
             uint8_t* const bdst = fdst + produced;
@@ -1279,7 +1279,7 @@ gc_zstd_dec_place_kernel(const GcZdFrame* __restrict__ frames, uint32_t nFrames,
             if (!status) {
                 if (ty & GC_ZD_B_BAD) status = GC_ZD_CORRUPT;
                 else if (bt == 2u && (sIn[k][1] || sIn[k][2])) status = sIn[k][1] ? sIn[k][1] : sIn[k][2];
-                else if (produced + size > cap) status = GC_ZD_DST_SMALL;
+                else if (produced + size > cap) status = (fr.flags & GC_ZD_F_SIZE_KNOWN) ? GC_ZD_SIZE : GC_ZD_DST_SMALL;
             }
             GcZdPlace pl; pl.dst = produced; pl.rep[0] = r0; pl.rep[1] = r1; pl.rep[2] = r2; pl.skip = status ? 1u : 0u;
             sOut[k] = pl;
