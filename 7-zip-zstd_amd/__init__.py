@@ -35,7 +35,8 @@ EXPORTS = ["gc_test_hooks_enabled", "gc_lzfind_get_matches_device", "gc_device_c
            "gc_brotli_scan_prefix", "gc_brotli_dec_set_dictionary", "gc_brotli_dec_has_dictionary", "gc_brotli_decompress_device", "gc_brotli_decompress_host", "gc_brotli_decompress_timing",
            "gc_lzma2_scan_prefix", "gc_lzma2_decompress_device", "gc_lzma2_decompress_host", "gc_lzma2_decompress_timing",
            "gc_crc64_device", "gc_crc_segments_device", "gc_xz_compress_bound", "gc_xz_compress_device", "gc_xz_compress_host", "gc_xz_scan", "gc_xz_decompress_device", "gc_xz_decompress_host",
-           "gc_xz_timing", "gc_xz_launch_counts"]
+           "gc_xz_timing", "gc_xz_launch_counts",
+           "gc_zstd_batch_compress_bound", "gc_zstd_batch_compress_device", "gc_zstd_batch_finish", "gc_zstd_batch_compress_host", "gc_zstd_batch_timing", "gc_zstd_batch_round_items"]
 
 CODEC_ZSTD, CODEC_FLZMA2, CODEC_BROTLI = 0, 1, 2
 CODEC_IDS = {"zstd": CODEC_ZSTD, "flzma2": CODEC_FLZMA2, "brotli": CODEC_BROTLI}
@@ -232,6 +233,16 @@ class ZstdFrame(C.Structure):
     """gc_zstd_frame of include/gpucodec.h"""
     _fields_ = [("src_off", C.c_uint64), ("src_size", C.c_uint64), ("dst_off", C.c_uint64), ("content_size", C.c_uint64),
                 ("flags", C.c_uint32), ("header_size", C.c_uint32), ("n_blocks", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BatchItem(C.Structure):
+    """gc_batch_item of include/gpucodec.h: bytes [src_off, src_off + src_size) of the batch call's input"""
+    _fields_ = [("src_off", C.c_uint64), ("src_size", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BatchResult(C.Structure):
+    """gc_batch_result of include/gpucodec.h: where item i's frame lies in the packed output; flags bit 0: stored as a raw block"""
+    _fields_ = [("dst_off", C.c_uint64), ("dst_size", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class BrotliChunk(C.Structure):
@@ -740,6 +751,31 @@ class ZstdDecoder(_EncoderBase):
         self._check(self._lib.gc_zstd_decompress_host(self._ctx, a.ctypes.data, a.size, out.ctypes.data, cap, C.byref(n)), "gc_zstd_decompress_host")
         return out[:n.value]
 
+    def code_batch(self, frames):
+        """list of zstd frames (bytes-like, each stating its content size: what ZstdEncoder.code_batch returns) -> list of numpy uint8 contents.
+        The frames are concatenated, scanned and decoded in ONE decode call, and the content is cut at the frames' content sizes."""
+        import numpy as np
+        parts = [np.frombuffer(f, dtype=np.uint8) if not isinstance(f, np.ndarray) else f.astype(np.uint8, copy=False).ravel() for f in frames]
+        if not parts:
+            return []
+        a = np.concatenate(parts)
+        table, nf, total = self.scan(a)
+        if total is None:
+            raise GpuCodecError("code_batch: a frame does not state its content size")
+        content = self.code(a)
+        if content.size != total:
+            raise GpuCodecError("code_batch: decoded %d bytes, the frames state %d" % (content.size, total))
+        # a part may hold several frames (and skippable ones): its content is that of the frames that start inside it
+        ends, out, k, pos = np.cumsum([q.size for q in parts]), [], 0, 0
+        for end in ends:
+            n = 0
+            while k < nf and table[k].src_off < end:
+                n += table[k].content_size
+                k += 1
+            out.append(content[pos:pos + n])
+            pos += n
+        return out
+
     def code_device(self, d_src_ptr, n, d_dst_ptr, dst_cap, frames, n_frames):
         size = C.c_size_t(0)
         self._check(self._lib.gc_zstd_decompress_device(self._ctx, d_src_ptr, n, d_dst_ptr, dst_cap, frames, n_frames, C.byref(size)), "gc_zstd_decompress_device")
@@ -808,6 +844,86 @@ class ZstdEncoder(_EncoderBase):
         ms = (C.c_float * 6)()
         self._check(self._lib.gc_zstd_last_timing(self._ctx, ms), "gc_zstd_last_timing")
         return dict(zip(self.KERNELS, [float(x) for x in ms]))
+
+    # ---- batches: many independent inputs of at most BATCH_ITEM_MAX bytes, one frame each, in one launch set (include/gpucodec.h "ZSTD, batched")
+    BATCH_ITEM_MAX = 128 << 10
+    BATCH_KERNELS = ("lz", "entropy", "frame", "total")
+
+    def _batch_protos(self):
+        L = self._lib
+        L.gc_zstd_batch_compress_bound.argtypes = [C.c_void_p, C.c_size_t]
+        L.gc_zstd_batch_compress_bound.restype = C.c_size_t
+        L.gc_zstd_batch_compress_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int]
+        L.gc_zstd_batch_compress_device.restype = C.c_int
+        L.gc_zstd_batch_finish.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+        L.gc_zstd_batch_finish.restype = C.c_int
+        L.gc_zstd_batch_compress_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_size_t)]
+        L.gc_zstd_batch_compress_host.restype = C.c_int
+        L.gc_zstd_batch_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.gc_zstd_batch_timing.restype = C.c_int
+        L.gc_zstd_batch_round_items.argtypes = [C.c_void_p]
+        L.gc_zstd_batch_round_items.restype = C.c_size_t
+        return L
+
+    def batch_round_items(self):
+        """items one round of a batch call takes through the workspace (a larger batch runs in several rounds, one behind the other)"""
+        return self._batch_protos().gc_zstd_batch_round_items(self._ctx)
+
+    def batch_bound(self, sizes):
+        """destination capacity that always suffices for items of these sizes"""
+        sizes = list(sizes)
+        items = (BatchItem * max(1, len(sizes)))()
+        for i, n in enumerate(sizes):
+            items[i].src_size = int(n)
+        return self._batch_protos().gc_zstd_batch_compress_bound(items, len(sizes))
+
+    def code_batch_host(self, buffers):
+        """list of bytes-like / numpy uint8 (each at most BATCH_ITEM_MAX bytes) -> (packed frames as numpy uint8, list of BatchResult): one H2D copy,
+        one launch set, one D2H copy of the frames and one of the table"""
+        import numpy as np
+        arrs = [np.ascontiguousarray(np.frombuffer(b, dtype=np.uint8) if not isinstance(b, np.ndarray) else b, dtype=np.uint8) for b in buffers]
+        n = len(arrs)
+        srcs = (C.c_void_p * max(1, n))(*[a.ctypes.data for a in arrs])
+        sizes = (C.c_size_t * max(1, n))(*[a.size for a in arrs])
+        cap = self.batch_bound([a.size for a in arrs])
+        out = np.empty(max(1, cap), dtype=np.uint8)
+        results = (BatchResult * max(1, n))()
+        total = C.c_size_t(0)
+        rc = self._batch_protos().gc_zstd_batch_compress_host(self._ctx, srcs, sizes, n, out.ctypes.data, cap, self.level, results, C.byref(total))
+        self._check(rc, "gc_zstd_batch_compress_host")
+        return out[:total.value], list(results[:n])
+
+    def code_batch(self, buffers):
+        """list of bytes-like / numpy uint8 -> list of bytes: item i's zstd frame, the bytes code() gives for that item alone"""
+        out, results = self.code_batch_host(buffers)
+        return [out[r.dst_off:r.dst_off + r.dst_size].tobytes() for r in results]
+
+    def code_batch_device(self, d_src_ptr, src_bytes, items, d_dst_ptr, dst_cap):
+        """Enqueue a batch over device memory.  items: a ctypes array of BatchItem, or a sequence of (src_off, src_size) pairs (host memory; the context
+        keeps its own copy until finish_batch)."""
+        if not isinstance(items, C.Array):
+            pairs = list(items)
+            items = (BatchItem * max(1, len(pairs)))()
+            for i, (off, size) in enumerate(pairs):
+                items[i].src_off, items[i].src_size = int(off), int(size)
+            n = len(pairs)
+        else:
+            n = len(items)
+        rc = self._batch_protos().gc_zstd_batch_compress_device(self._ctx, d_src_ptr, src_bytes, items, n, d_dst_ptr, dst_cap, self.level)
+        self._check(rc, "gc_zstd_batch_compress_device")
+
+    def finish_batch(self, n_items):
+        """-> (list of BatchResult, total bytes) of the pending batch call"""
+        results = (BatchResult * max(1, n_items))()
+        total = C.c_size_t(0)
+        self._check(self._batch_protos().gc_zstd_batch_finish(self._ctx, results, C.byref(total)), "gc_zstd_batch_finish")
+        return list(results[:n_items]), total.value
+
+    def batch_timing_ms(self):
+        """HIP-event times of the last batch call, summed over its rounds: finder, entropy stages, plan + emit; total = first kernel start -> last kernel end"""
+        ms = (C.c_float * 4)()
+        self._check(self._batch_protos().gc_zstd_batch_timing(self._ctx, ms), "gc_zstd_batch_timing")
+        return dict(zip(self.BATCH_KERNELS, [float(x) for x in ms]))
 
     CHECKSUM = 8                      # GC_ZSTD_CHECKSUM: per-call flag of code_pre / MultiEncoder.code
 

@@ -46,6 +46,13 @@ extern "C" __global__ void gc_zstd_plan_kernel(const GcSectionInfo*, uint32_t, u
 extern "C" __global__ void gc_zstd_emit_kernel(const uint8_t*, uint64_t, const uint8_t*, const uint8_t*, const GcSectionInfo*,
                                                const GcFramePlan*, const uint64_t*, uint32_t, uint32_t, uint8_t*, const uint64_t*);
 extern "C" __global__ void gc_zstd_xxh64_kernel(const uint8_t*, uint64_t, uint64_t, uint32_t, uint64_t, uint64_t*);      // K0x (gc_xxh64.h)
+// the batch forms of K1, K3d, K4, K5 and K0x: an item table where the others derive a block's place and length from the stream's size (gc_zstd_batch.h)
+extern "C" __global__ void gc_zstd_lz_batch_kernel(const uint8_t*, const gc_batch_item*, GcSeqRaw*, uint8_t*, GcBlockMeta*);
+extern "C" __global__ void gc_zstd_seq_pack_batch_kernel(const uint64_t*, const uint8_t*, const uint16_t*, const GcSeqTabG*, uint8_t*, GcSectionInfo*, const gc_batch_item*);
+extern "C" __global__ void gc_zstd_plan_batch_kernel(const GcSectionInfo*, const gc_batch_item*, uint32_t, uint64_t, GcFramePlan*, gc_batch_result*, uint64_t*, uint32_t);
+extern "C" __global__ void gc_zstd_emit_batch_kernel(const uint8_t*, const gc_batch_item*, const uint8_t*, const uint8_t*, const GcSectionInfo*, const GcFramePlan*, const uint64_t*,
+                                                     uint8_t*, const uint64_t*);
+extern "C" __global__ void gc_zstd_xxh64_batch_kernel(const uint8_t*, const gc_batch_item*, uint64_t*);
 
 extern "C" __global__ void gc_mf_count_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t*);
 extern "C" __global__ void gc_mf_scan_kernel(uint32_t*, uint32_t);
@@ -162,6 +169,12 @@ struct gc_ctx {
     uint32_t zdRounds = 0; hipEvent_t zdEv[2] = {}; float zdMs = 0.f; float zdKms[4] = {};      // last call: whole, and index / literals / sequences / execution kernels
     int zdSeqvState = 0;      // 0 not checked yet, 1 verified on this device, -1 wrong: the one-block-per-wave kernel is used
     bool zdSelfTest = false;
+    // zstd batches (gc_zstd_batch.h): the item table and the result table of the pending call in device memory, the running output offset / "too small" mark that
+    // carries from round to round, the host's copy of the items and the gather buffer of the host entry (pinned), events (GC_BT_EVENTS per round, grown on demand)
+    GcBuf<gc_batch_item> btItems; GcBuf<gc_batch_result> btResults; GcBuf<uint64_t> btResult;
+    gc_batch_item* btHostItems = nullptr; size_t btHostItemsCap = 0; uint8_t* btHostStage = nullptr; size_t btHostStageCap = 0;
+    size_t btN = 0; bool btPending = false, btTimed = false;
+    hipEvent_t* btEv = nullptr; uint32_t btEvRounds = 0, btRounds = 0; hipEvent_t btEvCall[3] = {};      // (call: start, K0x end, end)
     GcBuf<unsigned long long> prof;  // GC_LZ_PHASES + GC_SEQ_PHASES cycle sums, only when profiling is on
     bool profOn = false; uint32_t profBlocks = 0;
 };
@@ -212,6 +225,7 @@ void gc_l2d_release(GcL2dWork* w);
 int gc_l2d_decode(hipStream_t st, GcL2dWork* w, const uint8_t* d_src, size_t n, const gc_lzma2_unit* units, size_t nUnits, uint8_t* d_dst, size_t dstCap, unsigned dictProp,
                   size_t* produced, char* err, size_t errCap);
 static void ctx_release(gc_ctx* c);
+static void batch_release(gc_ctx* c);      // (gc_zstd_batch.h)
 
 extern "C" int gc_ctx_create(gc_ctx** out, int device)
 {
@@ -253,6 +267,7 @@ static void ctx_release(gc_ctx* c)
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->streamHash) hipStreamSynchronize(c->streamHash);
     if (c->hostResult) hipHostFree(c->hostResult);
+    batch_release(c);
     gc_brd_release(&c->brd);
     gc_l2d_release(&c->l2d);
     for (int i = 0; i < 2; i++) if (c->zdEv[i]) hipEventDestroy(c->zdEv[i]);
@@ -292,7 +307,8 @@ extern "C" void* gc_ctx_stream(gc_ctx* c) { return c ? (void*)c->stream : nullpt
 
 // The per-block workspace: room for nBlocks blocks in every row, or none of it (nBlocks == 0, and after a failed growth).  capBlocks says what the rows hold --
 // it is also the stride of lzProps' second half (gc_flzma2_compress_device: segKind).
-static int workspace_resize(gc_ctx* c, uint32_t nBlocks)
+// bytesPerBlock != null: nothing is resized, *bytesPerBlock = what one block takes over all rows (the batch calls size their rounds by it: gc_zstd_batch.h)
+static int workspace_resize(gc_ctx* c, uint32_t nBlocks, size_t* bytesPerBlock = nullptr)
 {
     const size_t ms = GC_MAX_SEQ_PER_BLOCK;
     const struct { GcBufRaw& buf; size_t perBlock; } rows[] = {
@@ -302,6 +318,7 @@ static int workspace_resize(gc_ctx* c, uint32_t nBlocks)
         { c->brStage, GC_BR_STAGE_STRIDE }, { c->brInfo, sizeof(GcBrotliBlockInfo) }, { c->brPlan, sizeof(GcBrotliPlan) },
         { c->lzProps, 2u * (GC_ZSTD_BLOCK_MAX >> GC_LZMA_SEG_LOG_MIN) },      // (second half: LZMA / stored per model segment, gc_lzma2_segkind_kernel)
         { c->lzNM, sizeof(uint32_t) }, { c->lzInfo, GC_LZMA_RC_PER_BLOCK * sizeof(GcLzmaChunkInfo) }, { c->lzPlan, GC_LZMA_RC_PER_BLOCK * sizeof(GcLzmaPlan) } };
+    if (bytesPerBlock) { *bytesPerBlock = 0; for (auto& r : rows) *bytesPerBlock += r.perBlock; return GC_OK; }
     c->capBlocks = 0;
     for (auto& r : rows) {
         if (!nBlocks) gc_buf_release(r.buf);
@@ -1751,3 +1768,4 @@ extern "C" int gc_lzma2_decompress_timing(gc_ctx* c, float* ms) { if (!c || !ms)
 
 // ---- the .xz container: reader, writer and their entry points
 #include "gc_xz.h"
+#include "gc_zstd_batch.h"

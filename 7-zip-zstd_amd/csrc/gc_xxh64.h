@@ -15,6 +15,7 @@
 #pragma once
 #include "gc_common.h"
 #include "gc_device.h"
+#include "gpucodec.h"      // gc_batch_item
 
 #define XXH_T        GC_XXH64_T                    // wave 0 chains, waves 1..4 stage
 #define XXH_STAGERS  (XXH_T - 64u)
@@ -47,17 +48,14 @@ __device__ __forceinline__ void xx_stage(const uint8_t* __restrict__ p, uint64_t
         for (uint32_t w = s; w < words; w += XXH_STAGERS) prod[w] = gc_ld64(p + base + 8ull * w) * XXP2;
 }
 
-// frame f = bytes [f * frameBytes, min(srcSize, (f + 1) * frameBytes)) of src; out[f] = XXH64(frame, seed)
-extern "C" __global__ void __launch_bounds__(XXH_T)
-gc_zstd_xxh64_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, uint64_t frameBytes, uint32_t nFrames, uint64_t seed, uint64_t* __restrict__ out)
+struct XxLds { uint64_t prod[2][XXH_WORDS]; uint64_t acc[4]; };      // the calling kernel's LDS: staged products (double buffered), the four accumulators
+
+// out[0] = XXH64(len bytes at p, seed), by the whole workgroup
+__device__ __forceinline__ void xx_frame(const uint8_t* __restrict__ const p, const uint64_t len, const uint64_t seed, uint64_t* __restrict__ out, XxLds& L)
 {
-    __shared__ uint64_t sProd[2][XXH_WORDS];
-    __shared__ uint64_t sAcc[4];
-    const uint32_t t = threadIdx.x, f = blockIdx.x;
-    if (f >= nFrames) return;
-    const uint64_t start = (uint64_t)f * frameBytes;
-    const uint64_t len = (srcSize - start) < frameBytes ? (srcSize - start) : frameBytes;
-    const uint8_t* const p = src + start;
+    uint64_t (&sProd)[2][XXH_WORDS] = L.prod;
+    uint64_t (&sAcc)[4] = L.acc;
+    const uint32_t t = threadIdx.x;
     const uint64_t stripeBytes = len & ~31ull;
     const uint64_t nTiles = (stripeBytes + XXH_TILE - 1u) / XXH_TILE;
     uint64_t acc = seed + (t == 0u ? XXP1 + XXP2 : (t == 1u ? XXP2 : (t == 2u ? 0ull : 0ull - XXP1)));
@@ -89,6 +87,26 @@ gc_zstd_xxh64_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, uint64_t
         if (pos + 4u <= len) { h ^= (uint64_t)gc_ld32(p + pos) * XXP1; h = xx_rotl(h, 23) * XXP2 + XXP3; pos += 4u; }
         while (pos < len) { h ^= (uint64_t)p[pos] * XXP5; h = xx_rotl(h, 11) * XXP1; pos++; }
         h ^= h >> 33; h *= XXP2; h ^= h >> 29; h *= XXP3; h ^= h >> 32;
-        out[f] = h;
+        out[0] = h;
     }
+}
+
+// frame f = bytes [f * frameBytes, min(srcSize, (f + 1) * frameBytes)) of src; out[f] = XXH64(frame, seed)
+extern "C" __global__ void __launch_bounds__(XXH_T)
+gc_zstd_xxh64_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, uint64_t frameBytes, uint32_t nFrames, uint64_t seed, uint64_t* __restrict__ out)
+{
+    __shared__ XxLds L;
+    const uint32_t f = blockIdx.x;
+    if (f >= nFrames) return;
+    const uint64_t start = (uint64_t)f * frameBytes;
+    xx_frame(src + start, (srcSize - start) < frameBytes ? (srcSize - start) : frameBytes, seed, out + f, L);
+}
+
+// K0x of a batch (gc_zstd_batch.h): frame f = item f of the table, seed 0
+extern "C" __global__ void __launch_bounds__(XXH_T)
+gc_zstd_xxh64_batch_kernel(const uint8_t* __restrict__ src, const gc_batch_item* __restrict__ items, uint64_t* __restrict__ out)
+{
+    __shared__ XxLds L;
+    const gc_batch_item it = items[blockIdx.x];
+    xx_frame(src + it.src_off, it.src_size, 0, out + blockIdx.x, L);
 }

@@ -27,6 +27,27 @@ __device__ __forceinline__ uint32_t frame_len_of(uint32_t b, uint32_t frameBlock
     const uint64_t start = (uint64_t)(b / frameBlocks) * fb;
     return (uint32_t)((srcSize - start) < fb ? (srcSize - start) : fb);
 }
+// bytes a block of blockLen content bytes takes in the output -- hdr bytes of frame header in front, the 3-byte block header, the two sections or, where they do not
+// beat it, the content itself (comp = 0), tail bytes of checksum behind
+__device__ __forceinline__ uint32_t frame_block_size(const GcSectionInfo si, uint32_t blockLen, uint32_t hdr, uint32_t tail, uint32_t& comp)
+{
+    const uint64_t payload = (uint64_t)si.litSecSize + si.seqSecSize;
+    comp = (si.seqSecSize != 0xFFFFFFFFu && payload < blockLen) ? 1u : 0u;
+    return hdr + 3u + (comp ? (uint32_t)payload : blockLen) + tail;
+}
+// exclusive prefix sum of `size` over the 1024 threads of the workgroup (sWave: 16 words of LDS; both barriers inside); *all = the sum
+__device__ __forceinline__ uint32_t frame_excl_scan(uint32_t size, uint32_t* sWave, uint32_t* all)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t incl = gc_wave_incl_sum(size);
+    if (lane == 63u) sWave[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, sum = 0;
+    for (uint32_t w = 0; w < 16u; w++) { uint32_t c = sWave[w]; if (w < wave) before += c; sum += c; }
+    __syncthreads();
+    *all = sum;
+    return before + incl - size;
+}
 
 // K4: one workgroup; exclusive scan of frame sizes
 extern "C" __global__ void __launch_bounds__(1024)
@@ -36,7 +57,7 @@ gc_zstd_plan_kernel(const GcSectionInfo* __restrict__ info, uint32_t nBlocks, ui
                     uint32_t checksum /* 1: every frame ends with its content checksum, and the seek table lists them */)
 {
     __shared__ uint32_t sWave[16];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const uint32_t t = threadIdx.x;
     uint64_t carry = 0;
     for (uint32_t tb = 0; tb < nBlocks; tb += 1024u) {
         const uint32_t b = tb + t;
@@ -44,26 +65,55 @@ gc_zstd_plan_kernel(const GcSectionInfo* __restrict__ info, uint32_t nBlocks, ui
         if (b < nBlocks) {
             const uint64_t base = (uint64_t)b * GC_ZSTD_BLOCK_MAX;
             const uint32_t blockLen = (uint32_t)((srcSize - base) < GC_ZSTD_BLOCK_MAX ? (srcSize - base) : GC_ZSTD_BLOCK_MAX);
-            const GcSectionInfo si = info[b];
-            const uint64_t payload = (uint64_t)si.litSecSize + si.seqSecSize;
-            comp = (si.seqSecSize != 0xFFFFFFFFu && payload < blockLen) ? 1u : 0u;
             const uint32_t hdr = (b % frameBlocks) == 0u ? frame_hdr_size(frame_len_of(b, frameBlocks, srcSize)) : 0u;
             const bool last = (b % frameBlocks) == frameBlocks - 1u || b == nBlocks - 1u;
-            size = hdr + 3u + (comp ? (uint32_t)payload : blockLen) + ((checksum && last) ? 4u : 0u);
+            size = frame_block_size(info[b], blockLen, hdr, (checksum && last) ? 4u : 0u, comp);
         }
-        uint32_t incl = gc_wave_incl_sum(size);
-        if (lane == 63u) sWave[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-        for (uint32_t w = 0; w < 16u; w++) { uint32_t c = sWave[w]; if (w < wave) before += c; all += c; }
-        __syncthreads();
-        if (b < nBlocks) { GcFramePlan p; p.off = carry + before + incl - size; p.size = size; p.compressed = comp; plan[b] = p; }
+        uint32_t all;
+        const uint32_t before = frame_excl_scan(size, sWave, &all);
+        if (b < nBlocks) { GcFramePlan p; p.off = carry + before; p.size = size; p.compressed = comp; plan[b] = p; }
         carry += all;
     }
     if (t == 0) {
         const uint32_t nFrames = (nBlocks + frameBlocks - 1u) / frameBlocks;
         const uint64_t total = carry + (seekTable ? 8ull + (checksum ? 12ull : 8ull) * nFrames + 9ull : 0ull);
         result[0] = total; result[1] = total > dstCap ? 1u : 0u;
+    }
+}
+
+// One block of a frame, by the whole workgroup: [frame header] block header, payload (the two sections, or the blockLen content bytes at `s` where K4 chose the raw
+// block) [, content checksum].  o = where K4 put the block; first / last: of its frame, whose content is frameLen bytes; hash: the frame's XXH64, or null.
+__device__ __forceinline__ void frame_write_block(uint8_t* __restrict__ o, const GcFramePlan p, const GcSectionInfo si, const bool first, const bool last, const uint32_t frameLen,
+                                                  const uint32_t blockLen, const uint8_t* __restrict__ s, const uint8_t* __restrict__ ls, const uint8_t* __restrict__ ss,
+                                                  const uint64_t* __restrict__ hash)
+{
+    const uint32_t t = threadIdx.x;
+    const uint32_t hs = first ? frame_hdr_size(frameLen) : 0u;
+    if (t == 0) {
+        if (first) {
+            o[0] = 0x28; o[1] = 0xB5; o[2] = 0x2F; o[3] = 0xFD;                     // ZSTD_MAGICNUMBER 0xFD2FB528
+            const uint32_t fcsCode = hs == 6u ? 0u : (hs == 7u ? 1u : 2u);
+            o[4] = (uint8_t)((fcsCode << 6) | (1u << 5) | (hash ? 1u << 2 : 0u));    // single segment, [content checksum,] no dictID
+            if (hs == 6u) o[5] = (uint8_t)frameLen;
+            else if (hs == 7u) { uint32_t v = frameLen - 256u; o[5] = (uint8_t)v; o[6] = (uint8_t)(v >> 8); }
+            else { o[5] = (uint8_t)frameLen; o[6] = (uint8_t)(frameLen >> 8); o[7] = (uint8_t)(frameLen >> 16); o[8] = (uint8_t)(frameLen >> 24); }
+        }
+        const uint32_t bsz = p.compressed ? si.litSecSize + si.seqSecSize : blockLen;
+        const uint32_t bh = (last ? 1u : 0u) | ((p.compressed ? 2u : 0u) << 1) | (bsz << 3);  // last block, type, size
+        o[hs] = (uint8_t)bh; o[hs + 1u] = (uint8_t)(bh >> 8); o[hs + 2u] = (uint8_t)(bh >> 16);
+        if (hash && last) {                                                          // the frame's last four bytes (K4 counted them into p.size)
+            const uint32_t h = (uint32_t)*hash;
+            uint8_t* e = o + p.size - 4u;
+            e[0] = (uint8_t)h; e[1] = (uint8_t)(h >> 8); e[2] = (uint8_t)(h >> 16); e[3] = (uint8_t)(h >> 24);
+        }
+    }
+    uint8_t* pay = o + hs + 3u;
+    if (p.compressed) {
+        for (uint32_t i = t; i < si.litSecSize; i += FRAME_T) pay[i] = ls[i];
+        pay += si.litSecSize;
+        for (uint32_t i = t; i < si.seqSecSize; i += FRAME_T) pay[i] = ss[i];
+    } else {
+        for (uint32_t i = t; i < blockLen; i += FRAME_T) pay[i] = s[i];
     }
 }
 
@@ -99,39 +149,53 @@ gc_zstd_emit_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, const uin
     }
     const uint64_t base = (uint64_t)b * GC_ZSTD_BLOCK_MAX;
     const uint32_t blockLen = (uint32_t)((srcSize - base) < GC_ZSTD_BLOCK_MAX ? (srcSize - base) : GC_ZSTD_BLOCK_MAX);
-    const GcFramePlan p = plan[b];
-    const GcSectionInfo si = info[b];
-    uint8_t* o = dst + p.off;
     const bool first = (b % frameBlocks) == 0u, last = (b % frameBlocks) == frameBlocks - 1u || b == nBlocks - 1u;
-    const uint32_t frameLen = frame_len_of(b, frameBlocks, srcSize);
-    const uint32_t hs = first ? frame_hdr_size(frameLen) : 0u;
-    if (t == 0) {
-        if (first) {
-            o[0] = 0x28; o[1] = 0xB5; o[2] = 0x2F; o[3] = 0xFD;                     // ZSTD_MAGICNUMBER 0xFD2FB528
-            const uint32_t fcsCode = hs == 6u ? 0u : (hs == 7u ? 1u : 2u);
-            o[4] = (uint8_t)((fcsCode << 6) | (1u << 5) | (hash ? 1u << 2 : 0u));    // single segment, [content checksum,] no dictID
-            if (hs == 6u) o[5] = (uint8_t)frameLen;
-            else if (hs == 7u) { uint32_t v = frameLen - 256u; o[5] = (uint8_t)v; o[6] = (uint8_t)(v >> 8); }
-            else { o[5] = (uint8_t)frameLen; o[6] = (uint8_t)(frameLen >> 8); o[7] = (uint8_t)(frameLen >> 16); o[8] = (uint8_t)(frameLen >> 24); }
+    frame_write_block(dst + plan[b].off, plan[b], info[b], first, last, frame_len_of(b, frameBlocks, srcSize), blockLen, src + base,
+                      litSec + (uint64_t)b * GC_LITSEC_STRIDE, seqSec + (uint64_t)b * GC_SEQSEC_STRIDE, hash ? hash + b / frameBlocks : nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ batch forms (gc_zstd_batch.h)
+// A batch runs in rounds of nRound items through the per-block workspace: block b of the workspace holds item b of `items` (the round's part of the item table), every
+// item a frame of one block.  The output offset carries from round to round in result[0], the "too small" mark in result[1] stays once set; the host zeroes both
+// in front of the first round.
+
+// K4b: one workgroup; places the round's frames behind those of the rounds before and publishes { offset, size, raw } per item for the host to read back
+extern "C" __global__ void __launch_bounds__(1024)
+gc_zstd_plan_batch_kernel(const GcSectionInfo* __restrict__ info, const gc_batch_item* __restrict__ items, uint32_t nRound, uint64_t dstCap,
+                          GcFramePlan* __restrict__ plan, gc_batch_result* __restrict__ results /* the round's part of the result table */,
+                          uint64_t* __restrict__ result /* [0] bytes so far, [1] error */, uint32_t checksum)
+{
+    __shared__ uint32_t sWave[16];
+    const uint32_t t = threadIdx.x;
+    uint64_t carry = result[0];
+    const uint64_t err = result[1];
+    for (uint32_t tb = 0; tb < nRound; tb += 1024u) {
+        const uint32_t b = tb + t;
+        uint32_t size = 0, comp = 0;
+        if (b < nRound) {
+            const uint32_t blockLen = items[b].src_size;
+            size = frame_block_size(info[b], blockLen, frame_hdr_size(blockLen), checksum ? 4u : 0u, comp);
         }
-        const uint32_t bsz = p.compressed ? si.litSecSize + si.seqSecSize : blockLen;
-        const uint32_t bh = (last ? 1u : 0u) | ((p.compressed ? 2u : 0u) << 1) | (bsz << 3);  // last block, type, size
-        o[hs] = (uint8_t)bh; o[hs + 1u] = (uint8_t)(bh >> 8); o[hs + 2u] = (uint8_t)(bh >> 16);
-        if (hash && last) {                                                          // the frame's last four bytes (K4 counted them into p.size)
-            const uint32_t h = (uint32_t)hash[b / frameBlocks];
-            uint8_t* e = o + p.size - 4u;
-            e[0] = (uint8_t)h; e[1] = (uint8_t)(h >> 8); e[2] = (uint8_t)(h >> 16); e[3] = (uint8_t)(h >> 24);
+        uint32_t all;
+        const uint32_t before = frame_excl_scan(size, sWave, &all);     // (its barriers also stand between every thread's read of result[] above and the write below)
+        if (b < nRound) {
+            GcFramePlan p; p.off = carry + before; p.size = size; p.compressed = comp; plan[b] = p;
+            gc_batch_result r; r.dst_off = p.off; r.dst_size = size; r.flags = comp ? 0u : 1u; results[b] = r;
         }
+        carry += all;
     }
-    uint8_t* pay = o + hs + 3u;
-    if (p.compressed) {
-        const uint8_t* ls = litSec + (uint64_t)b * GC_LITSEC_STRIDE;
-        const uint8_t* ss = seqSec + (uint64_t)b * GC_SEQSEC_STRIDE;
-        for (uint32_t i = t; i < si.litSecSize; i += FRAME_T) pay[i] = ls[i];
-        pay += si.litSecSize;
-        for (uint32_t i = t; i < si.seqSecSize; i += FRAME_T) pay[i] = ss[i];
-    } else {
-        const uint8_t* s = src + base;
-        for (uint32_t i = t; i < blockLen; i += FRAME_T) pay[i] = s[i];
-    }
+    if (t == 0) { result[0] = carry; result[1] = (err || carry > dstCap) ? 1u : 0u; }
+}
+
+// K5b: one workgroup per item writes its frame; the raw-block fallback copies from the item's place in the input
+extern "C" __global__ void __launch_bounds__(FRAME_T)
+gc_zstd_emit_batch_kernel(const uint8_t* __restrict__ src, const gc_batch_item* __restrict__ items, const uint8_t* __restrict__ litSec,
+                          const uint8_t* __restrict__ seqSec, const GcSectionInfo* __restrict__ info, const GcFramePlan* __restrict__ plan,
+                          const uint64_t* __restrict__ result, uint8_t* __restrict__ dst, const uint64_t* __restrict__ hash /* per item of the round, or null */)
+{
+    if (result[1]) return;                       // output buffer too small: this round and the ones behind it write nothing
+    const uint32_t b = blockIdx.x;
+    const gc_batch_item it = items[b];
+    frame_write_block(dst + plan[b].off, plan[b], info[b], true, true, it.src_size, it.src_size, src + it.src_off,
+                      litSec + (uint64_t)b * GC_LITSEC_STRIDE, seqSec + (uint64_t)b * GC_SEQSEC_STRIDE, hash ? hash + b : nullptr);
 }

@@ -24,28 +24,22 @@
 //
 // LDS: 64 KiB long table + 64 KiB short table + 8 KiB chunk table + 8 KiB parse scratch (1 workgroup / CU).
 #include "gc_lz_parse.h"
+#include "gpucodec.h"      // gc_batch_item
 
 #define LZ_LOG_L    14u              // long-hash table: 2^14 entries
 #define LZ_LOG_S    14u              // short-hash table
 #define LZ_LOG_C    11u              // chunk-local table
 #define LZ_TAG_BITS 15u
 
-extern "C" __global__ void __launch_bounds__(LZ_T)
-gc_zstd_lz_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, GcSeqRaw* __restrict__ seqRaw,
-                  uint8_t* __restrict__ lit, GcBlockMeta* __restrict__ meta,
-                  unsigned long long* __restrict__ prof /* optional: per-phase cycle sums (thread 0 of every block) */)
+// One block: bytes [base, base + n) of src; `end` is where the readable input ends for this block (the end of the whole stream for K1, the end of the
+// item for K1b): no byte at or behind src + end is read, and a position takes part in matching only if GC_MATCH_CAP + 16 bytes lie in front of `end`.
+// The LDS tables belong to the calling kernel (the same four for K1 and K1b: the matches depend on their geometry).
+__device__ __forceinline__ void lz_block(const uint8_t* __restrict__ src, const uint64_t base, const uint32_t n, const uint64_t end,
+                                         GcSeqRaw* __restrict__ mySeq, uint8_t* __restrict__ myLit, GcBlockMeta* __restrict__ myMeta,
+                                         unsigned long long* __restrict__ prof,
+                                         uint32_t (&tabL)[1u << LZ_LOG_L], uint32_t (&tabS)[1u << LZ_LOG_S], uint32_t (&tabC)[1u << LZ_LOG_C], LzParseLds& S)
 {
-    __shared__ uint32_t tabL[1u << LZ_LOG_L];
-    __shared__ uint32_t tabS[1u << LZ_LOG_S];
-    __shared__ uint32_t tabC[1u << LZ_LOG_C];
-    __shared__ LzParseLds S;
-
     const uint32_t t = threadIdx.x;
-    const uint32_t b = blockIdx.x;
-    const uint64_t base = (uint64_t)b * GC_ZSTD_BLOCK_MAX;
-    const uint32_t n = (uint32_t)((srcSize - base) < GC_ZSTD_BLOCK_MAX ? (srcSize - base) : GC_ZSTD_BLOCK_MAX);
-    GcSeqRaw* mySeq = seqRaw + (uint64_t)b * GC_MAX_SEQ_PER_BLOCK;
-    uint8_t* myLit = lit + (uint64_t)b * GC_ZSTD_BLOCK_MAX;
 
     for (uint32_t i = t; i < (1u << LZ_LOG_L); i += LZ_T) tabL[i] = 0;
     for (uint32_t i = t; i < (1u << LZ_LOG_S); i += LZ_T) tabS[i] = 0;
@@ -58,14 +52,14 @@ gc_zstd_lz_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, GcSeqRaw* _
     uint32_t totalSeq = 0, totalLit = 0;   // uniform running totals
     const uint32_t nChunks = (n + LZ_T - 1) / LZ_T;
     LzW16 own; own.a = 0; own.b = 0;                    // own 16 bytes, always loaded one chunk ahead
-    if (base + t + GC_MATCH_CAP + 16u <= srcSize) own = lz_ld16(src, base + t);
+    if (base + t + GC_MATCH_CAP + 16u <= end) own = lz_ld16(src, base + t);
 
     for (uint32_t k = 0; k < nChunks; k++) {
         const uint32_t cbase = k * LZ_T;
         const uint32_t p = cbase + t;
         const bool inBlock = p < n;
         // positions closer than 8 bytes to the block end, or without a readable compare window, stay literals
-        const bool canHash = p + 8u <= n && base + p + GC_MATCH_CAP + 16u <= srcSize;
+        const bool canHash = p + 8u <= n && base + p + GC_MATCH_CAP + 16u <= end;
 
         // ---- P0/P1: load, hash, probe
         uint32_t lo = 0, hi = 0, hL = 0, hS = 0, eL = 0, eS = 0;
@@ -108,12 +102,44 @@ gc_zstd_lz_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, GcSeqRaw* _
             lz_verify(src + base, p, me, cand, nc, maxLen, bestLen, bestOff);
         }
         // prefetch the next chunk's own bytes; the latency hides under the parse below
-        if (base + p + LZ_T + GC_MATCH_CAP + 16u <= srcSize) own = lz_ld16(src, base + p + LZ_T);
+        if (base + p + LZ_T + GC_MATCH_CAP + 16u <= end) own = lz_ld16(src, base + p + LZ_T);
         S.sM[t] = (bestOff << 8) | bestLen;
         __syncthreads();
         LZ_PHASE(P, 2);    // verify
         lz_parse_emit(S, P, cbase, inBlock, bestLen, bestOff, src + base, mySeq, myLit, totalSeq, totalLit);
     }
     if (prof && t == 0) for (int i = 0; i < GC_LZ_PHASES; i++) atomicAdd(&prof[i], P.pc[i]);
-    if (t == 0) { GcBlockMeta m; m.nSeqRaw = totalSeq; m.nLit = totalLit; meta[b] = m; }
+    if (t == 0) { GcBlockMeta m; m.nSeqRaw = totalSeq; m.nLit = totalLit; *myMeta = m; }
+}
+
+#define LZ_BLOCK_LDS \
+    __shared__ uint32_t tabL[1u << LZ_LOG_L]; \
+    __shared__ uint32_t tabS[1u << LZ_LOG_S]; \
+    __shared__ uint32_t tabC[1u << LZ_LOG_C]; \
+    __shared__ LzParseLds S
+
+// K1: block b = bytes [b * 128 KiB, ...) of one stream of srcSize bytes
+extern "C" __global__ void __launch_bounds__(LZ_T)
+gc_zstd_lz_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, GcSeqRaw* __restrict__ seqRaw,
+                  uint8_t* __restrict__ lit, GcBlockMeta* __restrict__ meta,
+                  unsigned long long* __restrict__ prof /* optional: per-phase cycle sums (thread 0 of every block) */)
+{
+    LZ_BLOCK_LDS;
+    const uint32_t b = blockIdx.x;
+    const uint64_t base = (uint64_t)b * GC_ZSTD_BLOCK_MAX;
+    const uint32_t n = (uint32_t)((srcSize - base) < GC_ZSTD_BLOCK_MAX ? (srcSize - base) : GC_ZSTD_BLOCK_MAX);
+    lz_block(src, base, n, srcSize, seqRaw + (uint64_t)b * GC_MAX_SEQ_PER_BLOCK, lit + (uint64_t)b * GC_ZSTD_BLOCK_MAX, meta + b, prof, tabL, tabS, tabC, S);
+}
+
+// K1b: workgroup b takes item b of a batch (gc_zstd_batch.h): bytes [src_off, src_off + src_size) of src, at most one block, at any alignment.  The item's end
+// stands where K1 has the stream's end, so nothing outside the item is read and the matches are those of a stream call on the item alone.
+extern "C" __global__ void __launch_bounds__(LZ_T)
+gc_zstd_lz_batch_kernel(const uint8_t* __restrict__ src, const gc_batch_item* __restrict__ items, GcSeqRaw* __restrict__ seqRaw,
+                        uint8_t* __restrict__ lit, GcBlockMeta* __restrict__ meta)
+{
+    LZ_BLOCK_LDS;
+    const uint32_t b = blockIdx.x;
+    const gc_batch_item it = items[b];
+    lz_block(src, it.src_off, it.src_size, it.src_off + it.src_size, seqRaw + (uint64_t)b * GC_MAX_SEQ_PER_BLOCK, lit + (uint64_t)b * GC_ZSTD_BLOCK_MAX, meta + b, nullptr,
+             tabL, tabS, tabC, S);
 }

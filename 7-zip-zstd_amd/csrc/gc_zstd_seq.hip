@@ -26,6 +26,7 @@
 #include "gc_common.h"
 #include "gc_device.h"
 #include "gc_fse.h"
+#include "gpucodec.h"      // gc_batch_item
 #ifdef HIPEMU
 #include <stdio.h>
 #include <stdlib.h>
@@ -462,20 +463,19 @@ gc_zstd_seq_chain_kernel(const uint8_t* __restrict__ codes, const GcSectionInfo*
 }
 
 // ------------------------------------------------------------------------------------------------ K3d pack
-extern "C" __global__ void __launch_bounds__(SEQ_T)
-gc_zstd_seq_pack_kernel(const uint64_t* __restrict__ seqPacked, const uint8_t* __restrict__ codes, const uint16_t* __restrict__ states,
-                        const GcSeqTabG* __restrict__ tabs, uint8_t* __restrict__ seqSec, GcSectionInfo* __restrict__ info, uint64_t srcSize,
-                        unsigned long long* __restrict__ prof)
+struct SeqPackLds { uint32_t wave[SEQ_T / 64u]; uint32_t tile[SEQ_TILE_WORDS]; uint32_t mode[3], log[3], fin[3], desc[3]; };      // the calling kernel's LDS
+
+// block b of the workspace, whose content is blockLen bytes long (a section that does not stay below that is given up: the block is stored raw)
+__device__ __forceinline__ void seq_pack_block(const uint64_t* __restrict__ seqPacked, const uint8_t* __restrict__ codes, const uint16_t* __restrict__ states,
+                                               const GcSeqTabG* __restrict__ tabs, uint8_t* __restrict__ seqSec, GcSectionInfo* __restrict__ info,
+                                               const uint32_t b, const uint32_t blockLen, unsigned long long* __restrict__ prof, SeqPackLds& L)
 {
-    __shared__ uint32_t sWave[SEQ_T / 64u];
-    __shared__ uint32_t sTile[SEQ_TILE_WORDS];
-    __shared__ uint32_t sMode[3], sLog[3], sFinal[3], sDesc[3];
-    const uint32_t t = threadIdx.x, b = blockIdx.x;
+    uint32_t* const sWave = L.wave; uint32_t* const sTile = L.tile;
+    uint32_t* const sMode = L.mode; uint32_t* const sLog = L.log; uint32_t* const sFinal = L.fin; uint32_t* const sDesc = L.desc;
+    const uint32_t t = threadIdx.x;
     const uint32_t nSeq = info[b].nSeq;
     if (nSeq == 0u) return;                                   // (the codes kernel has written the one-byte section)
     unsigned long long tprev = prof ? gc_clock() : 0ull;
-    const uint64_t blockBase = (uint64_t)b * GC_ZSTD_BLOCK_MAX;
-    const uint32_t blockLen = (uint32_t)((srcSize - blockBase) < GC_ZSTD_BLOCK_MAX ? (srcSize - blockBase) : GC_ZSTD_BLOCK_MAX);
     const uint64_t* P = seqPacked + (uint64_t)b * GC_MAX_SEQ_PER_BLOCK;
     const uint8_t* cLL = codes + (uint64_t)b * 3u * GC_MAX_SEQ_PER_BLOCK;
     const uint8_t* cOF = cLL + GC_MAX_SEQ_PER_BLOCK;
@@ -559,4 +559,26 @@ gc_zstd_seq_pack_kernel(const uint64_t* __restrict__ seqPacked, const uint8_t* _
     }
     SEQ_PHASE(4);         // pack
     if (t == 0) info[b].seqSecSize = overflow ? 0xFFFFFFFFu : hdrLen + outBytes;
+}
+
+extern "C" __global__ void __launch_bounds__(SEQ_T)
+gc_zstd_seq_pack_kernel(const uint64_t* __restrict__ seqPacked, const uint8_t* __restrict__ codes, const uint16_t* __restrict__ states,
+                        const GcSeqTabG* __restrict__ tabs, uint8_t* __restrict__ seqSec, GcSectionInfo* __restrict__ info, uint64_t srcSize,
+                        unsigned long long* __restrict__ prof)
+{
+    __shared__ SeqPackLds L;
+    const uint32_t b = blockIdx.x;
+    const uint64_t blockBase = (uint64_t)b * GC_ZSTD_BLOCK_MAX;
+    const uint32_t blockLen = (uint32_t)((srcSize - blockBase) < GC_ZSTD_BLOCK_MAX ? (srcSize - blockBase) : GC_ZSTD_BLOCK_MAX);
+    seq_pack_block(seqPacked, codes, states, tabs, seqSec, info, b, blockLen, prof, L);
+}
+
+// K3d of a batch (gc_zstd_batch.h): block b of the workspace holds item b, whose length comes from the item table
+extern "C" __global__ void __launch_bounds__(SEQ_T)
+gc_zstd_seq_pack_batch_kernel(const uint64_t* __restrict__ seqPacked, const uint8_t* __restrict__ codes, const uint16_t* __restrict__ states,
+                              const GcSeqTabG* __restrict__ tabs, uint8_t* __restrict__ seqSec, GcSectionInfo* __restrict__ info,
+                              const gc_batch_item* __restrict__ items)
+{
+    __shared__ SeqPackLds L;
+    seq_pack_block(seqPacked, codes, states, tabs, seqSec, info, blockIdx.x, items[blockIdx.x].src_size, nullptr, L);
 }

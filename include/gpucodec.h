@@ -211,6 +211,41 @@ int         gc_zstd_checksum_timing(gc_ctx* ctx, float* ms);
  * shipped one, which reads no environment variable at all */
 int         gc_test_hooks_enabled(void);
 
+/* ---- ZSTD, batched: many independent small inputs, one zstd frame each, all side by side in one launch set (the files of a non-solid archive, pages, records,
+ * the chunks of a key-value store).  A stream call on such an input is one workgroup's worth of work behind ten kernel launches, a size read-back and a
+ * synchronisation; a batch call runs item i as workgroup i of every stage.
+ *   The contract: item i compresses to exactly the bytes gc_zstd_compress_device writes for that item alone, at the same level and the same
+ * GC_OPT_ZSTD_CHECKSUM setting, with the seek table off -- one single-segment frame of one block that states its content size; an empty item gives the 9-byte
+ * (with checksums 13-byte) empty frame.  The frames lie packed in item order from d_dst; results[i] says where.  The whole output is a valid zstd stream whose
+ * content is the items concatenated: gc_zstd_scan_frames / gc_zstd_decompress_* and any zstd decoder take it as it is.
+ *   Items: `items` is host memory; the context copies it and owns the copy until gc_zstd_batch_finish.  Item i is bytes [src_off, src_off + src_size) of d_src
+ * (`reserved` is ignored): any offset, any alignment; items may leave gaps, overlap, repeat and come in any order -- the input is only read, and no byte outside
+ * an item is read for it.  An item larger than GC_ZSTD_BATCH_ITEM_MAX (one zstd block) or one that ends behind srcBytes is refused with GC_ERR_PARAM and a
+ * message that names its index and size: larger inputs belong to the stream entry points, whose windowed finder reaches back further than a block -- cutting
+ * them into block-local pieces here would quietly give a worse ratio, so it is refused, not degraded.
+ *   `level` is taken as in gc_zstd_compress_device (an input of one block runs the block-local finder at every level, so today it does not change the bytes).
+ * GC_OPT_ZSTD_CHECKSUM is honoured; GC_OPT_ZSTD_SEEK_TABLE is ignored by the batch calls: `results` is the table.
+ *   gc_zstd_batch_compress_device is asynchronous like gc_zstd_compress_device; gc_zstd_batch_finish synchronises, fills results[0 .. nItems) (host memory; may
+ * be null) and *totalSize.  nItems == 0 gives total 0 and GC_OK.  A dstCapacity below the total is reported by finish as GC_ERR_DST_SMALL; the frames of a
+ * batch that runs in one round (1636 items) are then not written at all -- of a larger batch the rounds in front of the one that ran out
+ * of room have written theirs.  gc_zstd_batch_compress_bound(items) is a capacity that always suffices.  finish without a pending batch call: GC_ERR_PARAM.
+ *   gc_zstd_batch_compress_host: the items are gathered into the context's staging buffer, ONE H2D copy carries the inputs, one D2H copy the frames and one the
+ * result table -- no per-item copies.  dst receives the packed frames.
+ *   gc_zstd_batch_timing (after finish): HIP-event times of the last batch call, summed over its rounds -- ms[0] finder (K1b), ms[1] entropy stages (literals
+ * and sequences, side by side on two streams), ms[2] plan + emit -- and a FOURTH entry, ms[3] = first kernel start -> last kernel end of the whole call. */
+#define GC_ZSTD_BATCH_ITEM_MAX (128u << 10)          /* one zstd block */
+typedef struct gc_batch_item   { uint64_t src_off; uint32_t src_size; uint32_t reserved; } gc_batch_item;   /* bytes [src_off, src_off + src_size) of d_src */
+typedef struct gc_batch_result { uint64_t dst_off; uint32_t dst_size; uint32_t flags; } gc_batch_result;    /* flags bit 0: stored as a raw block */
+size_t      gc_zstd_batch_compress_bound(const gc_batch_item* items, size_t nItems);
+int         gc_zstd_batch_compress_device(gc_ctx* ctx, const void* d_src, size_t srcBytes, const gc_batch_item* items, size_t nItems,
+                                          void* d_dst, size_t dstCapacity, int level);
+int         gc_zstd_batch_finish(gc_ctx* ctx, gc_batch_result* results /* nItems, host */, size_t* totalSize);
+int         gc_zstd_batch_compress_host(gc_ctx* ctx, const void* const* srcs, const size_t* sizes, size_t nItems, void* dst, size_t dstCapacity,
+                                        int level, gc_batch_result* results, size_t* totalSize);
+int         gc_zstd_batch_timing(gc_ctx* ctx, float ms[4]);
+/* items per round of this context's batch calls (DESIGN.md section 4 "Batches": what the workspace budget holds; 0 without a context) */
+size_t      gc_zstd_batch_round_items(gc_ctx* ctx);
+
 /* ---- CRC-32 of data that lies in device memory (C/7zCrc.c CrcCalc: polynomial 0xEDB88320, init and final XOR 0xFFFFFFFF).
  * Synchronous, on the current device's default stream. */
 int         gc_crc32_device(const void* d_src, size_t n, uint32_t* crc);
