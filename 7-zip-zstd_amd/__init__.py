@@ -36,7 +36,8 @@ EXPORTS = ["gc_test_hooks_enabled", "gc_lzfind_get_matches_device", "gc_device_c
            "gc_lzma2_scan_prefix", "gc_lzma2_decompress_device", "gc_lzma2_decompress_host", "gc_lzma2_decompress_timing",
            "gc_crc64_device", "gc_crc_segments_device", "gc_xz_compress_bound", "gc_xz_compress_device", "gc_xz_compress_host", "gc_xz_scan", "gc_xz_decompress_device", "gc_xz_decompress_host",
            "gc_xz_timing", "gc_xz_launch_counts",
-           "gc_zstd_batch_compress_bound", "gc_zstd_batch_compress_device", "gc_zstd_batch_finish", "gc_zstd_batch_compress_host", "gc_zstd_batch_timing", "gc_zstd_batch_round_items"]
+           "gc_zstd_batch_compress_bound", "gc_zstd_batch_compress_device", "gc_zstd_batch_finish", "gc_zstd_batch_compress_host", "gc_zstd_batch_timing", "gc_zstd_batch_round_items",
+           "gc_zstd_set_dictionary", "gc_zstd_dictionary_size"]
 
 CODEC_ZSTD, CODEC_FLZMA2, CODEC_BROTLI = 0, 1, 2
 CODEC_IDS = {"zstd": CODEC_ZSTD, "flzma2": CODEC_FLZMA2, "brotli": CODEC_BROTLI}
@@ -720,7 +721,29 @@ class XzDecoder(_EncoderBase):
         return int(v[0]), int(v[1]), int(v[2])
 
 
-class ZstdDecoder(_EncoderBase):
+class _ZstdDictionary:
+    """A raw-content zstd dictionary on the coder's context (include/gpucodec.h "ZSTD, dictionaries"): history in front of every item of ZstdEncoder's batch
+    calls and in front of every frame ZstdDecoder decodes.  Both sides must hold the same bytes."""
+    DICT_MAX = 128 << 10
+
+    def set_dictionary(self, data):
+        """bytes-like / numpy uint8 of 8 .. DICT_MAX bytes, or None (or empty) to remove the dictionary.  A formatted dictionary (magic 0xEC30A437) is refused."""
+        import numpy as np
+        if data is None:
+            a = np.zeros(0, np.uint8)
+        else:
+            a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+        self._lib.gc_zstd_set_dictionary.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        self._lib.gc_zstd_set_dictionary.restype = C.c_int
+        self._check(self._lib.gc_zstd_set_dictionary(self._ctx, a.ctypes.data if a.size else None, a.size), "gc_zstd_set_dictionary")
+
+    def dictionary_size(self):
+        self._lib.gc_zstd_dictionary_size.argtypes = [C.c_void_p]
+        self._lib.gc_zstd_dictionary_size.restype = C.c_size_t
+        return int(self._lib.gc_zstd_dictionary_size(self._ctx))
+
+
+class ZstdDecoder(_ZstdDictionary, _EncoderBase):
     """Mirror of NCompress::NZSTD::CDecoder (CPP/7zip/Compress/ZstdDecoder.cpp) for whole streams: frames decode concurrently on the GPU."""
     UNKNOWN = (1 << 64) - 1
 
@@ -810,7 +833,7 @@ class ZstdDecoder(_EncoderBase):
         return int(r.value)
 
 
-class ZstdEncoder(_EncoderBase):
+class ZstdEncoder(_ZstdDictionary, _EncoderBase):
     CODEC = 0
     """Mirror of NCompress::NZSTD::CEncoder for the compression hot path (one object per GPU)."""
 

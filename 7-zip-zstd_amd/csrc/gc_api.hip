@@ -48,6 +48,8 @@ extern "C" __global__ void gc_zstd_emit_kernel(const uint8_t*, uint64_t, const u
 extern "C" __global__ void gc_zstd_xxh64_kernel(const uint8_t*, uint64_t, uint64_t, uint32_t, uint64_t, uint64_t*);      // K0x (gc_xxh64.h)
 // the batch forms of K1, K3d, K4, K5 and K0x: an item table where the others derive a block's place and length from the stream's size (gc_zstd_batch.h)
 extern "C" __global__ void gc_zstd_lz_batch_kernel(const uint8_t*, const gc_batch_item*, GcSeqRaw*, uint8_t*, GcBlockMeta*);
+extern "C" __global__ void gc_zstd_lz_batch_dict_kernel(const uint8_t*, const gc_batch_item*, GcSeqRaw*, uint8_t*, GcBlockMeta*, const uint8_t*, uint32_t, const uint32_t*, const uint32_t*);
+extern "C" __global__ void gc_zstd_dict_digest_kernel(const uint8_t*, uint32_t, uint32_t*, uint32_t*);
 extern "C" __global__ void gc_zstd_seq_pack_batch_kernel(const uint64_t*, const uint8_t*, const uint16_t*, const GcSeqTabG*, uint8_t*, GcSectionInfo*, const gc_batch_item*);
 extern "C" __global__ void gc_zstd_plan_batch_kernel(const GcSectionInfo*, const gc_batch_item*, uint32_t, uint64_t, GcFramePlan*, gc_batch_result*, uint64_t*, uint32_t);
 extern "C" __global__ void gc_zstd_emit_batch_kernel(const uint8_t*, const gc_batch_item*, const uint8_t*, const uint8_t*, const GcSectionInfo*, const GcFramePlan*, const uint64_t*,
@@ -175,6 +177,8 @@ struct gc_ctx {
     gc_batch_item* btHostItems = nullptr; size_t btHostItemsCap = 0; uint8_t* btHostStage = nullptr; size_t btHostStageCap = 0;
     size_t btN = 0; bool btPending = false, btTimed = false;
     hipEvent_t* btEv = nullptr; uint32_t btEvRounds = 0, btRounds = 0; hipEvent_t btEvCall[3] = {};      // (call: start, K0x end, end)
+    // zstd raw-content dictionary (gc_zstd_set_dictionary): the bytes (zero-padded by GC_ZDICT_PAD), the two digest tables of K1b's dictionary variant; 0 = none
+    GcBuf<uint8_t> zdict; GcBuf<uint32_t> zdictTabL, zdictTabS; uint32_t zdictSize = 0;
     GcBuf<unsigned long long> prof;  // GC_LZ_PHASES + GC_SEQ_PHASES cycle sums, only when profiling is on
     bool profOn = false; uint32_t profBlocks = 0;
 };
@@ -790,6 +794,7 @@ extern "C" int gc_mf_pass_timing(gc_ctx* c, float ms[4])
 extern "C" int gc_zstd_compress_device(gc_ctx* c, const void* d_src, size_t n, void* d_dst, size_t dstCap, int level)
 {
     if (!c || (!d_src && n) || !d_dst) return GC_ERR_PARAM;
+    if (c->zdictSize) { snprintf(c->err, sizeof(c->err), "a dictionary is set: the zstd stream calls do not use one (only the batch calls do); remove it first"); return GC_ERR_UNSUPPORTED; }
     HIPCHK(c, hipSetDevice(c->device));
     c->timed = false;
     if (n == 0) {
@@ -1344,11 +1349,12 @@ extern "C" void gc_zstd_dec_launch_sequences(hipStream_t st, const uint8_t* src,
                                              unsigned long long* prof, const uint32_t* order, uint32_t* ready, int several);
 extern "C" void gc_zstd_dec_launch_exec(hipStream_t st, const uint8_t* src, uint64_t srcSize, uint8_t* dst, uint64_t dstCap, const GcZdFrame* frames, uint32_t nFrames,
                                         GcZdBlock* blocks, uint32_t* ticket, uint8_t* litWork, uint64_t litWorkSize, void* seqWork, uint64_t* result, unsigned long long* prof,
-                                        const uint32_t* ready);
+                                        const uint32_t* ready, const uint8_t* dict, uint32_t dictSize);
 
 extern "C" void gc_zstd_dec_launch_place(hipStream_t st, const GcZdFrame* frames, uint32_t nFrames, const GcZdBlock* blocks, uint64_t dstCap, GcZdPlace* place, uint64_t* result, uint32_t* ferr);
 extern "C" void gc_zstd_dec_launch_spread(hipStream_t st, const uint8_t* src, uint64_t srcSize, uint8_t* dst, const GcZdFrame* frames, const GcZdBlock* blocks, uint32_t nBlocks,
-                                          const GcZdPlace* place, const uint8_t* litWork, uint64_t litWorkSize, const void* seqWork, uint32_t* ptr, uint64_t batchBase, uint32_t* ferr);
+                                          const GcZdPlace* place, const uint8_t* litWork, uint64_t litWorkSize, const void* seqWork, uint32_t* ptr, uint64_t batchBase, uint32_t* ferr,
+                                          const uint8_t* dict, uint32_t dictSize);
 extern "C" void gc_zstd_dec_launch_chase(hipStream_t st, uint8_t* dstBatch, uint32_t* ptr, uint32_t n, uint32_t hops, uint8_t* pieceDone, uint32_t* counter);
 extern "C" void gc_zstd_dec_launch_finish(hipStream_t st, const uint8_t* src, const uint8_t* dst, const GcZdFrame* frames, uint32_t nFrames, uint64_t* result, const uint32_t* ferr);
 
@@ -1514,7 +1520,7 @@ extern "C" int gc_zstd_decompress_device(gc_ctx* c, const void* d_src, size_t n,
         hipStreamWaitEvent(c->stream3, c->evPart[0][0], 0);
         hipEventRecord(c->evPart[1][3], c->stream3);
         if (overlap) gc_zstd_dec_launch_exec(c->stream3, (const uint8_t*)d_src, n, (uint8_t*)d_dst, dstCap, c->zdFrames, (uint32_t)cnt, c->zdBlocks, c->zdTicket,
-                                             c->zdLit, litTot + 64u, c->zdSeq, c->zdResult, zdProf, c->zdReady);
+                                             c->zdLit, litTot + 64u, c->zdSeq, c->zdResult, zdProf, c->zdReady, c->zdict, c->zdictSize);
         hipEventRecord(c->evPart[1][2], c->stream2);
         gc_zstd_dec_launch_literals(c->stream2, (const uint8_t*)d_src, n, c->zdFrames, c->zdBlocks, (uint32_t)nBlocks, c->zdLit, zdProf, c->zdOrder, c->zdReady);
         hipEventRecord(c->evPart[0][1], c->stream2);
@@ -1541,7 +1547,7 @@ extern "C" int gc_zstd_decompress_device(gc_ctx* c, const void* d_src, size_t n,
         if (wide) {
             if (hipMemsetAsync(c->zdPtr, 0xFF, (size_t)padded * 4u, c->stream) != hipSuccess || hipMemsetAsync(c->zdDone, 0, (size_t)(padded / 1024u) + 16u, c->stream) != hipSuccess) { rc = GC_ERR_HIP; break; }
             gc_zstd_dec_launch_spread(c->stream, (const uint8_t*)d_src, n, (uint8_t*)d_dst, c->zdFrames, c->zdBlocks, (uint32_t)nBlocks, c->zdPlace, c->zdLit, litTot + 64u, c->zdSeq,
-                                      c->zdPtr, h[i].dstOff, c->zdFerr);
+                                      c->zdPtr, h[i].dstOff, c->zdFerr, c->zdict, c->zdictSize);
             uint32_t round = 0, hops = 0;                          // (0: the kernel's own number of links per round; test hook GC_ZD_HOPS)
             gc_env_u32("GC_ZD_HOPS", 1u, 64u, &hops);
             for (; extent && round < 64u; round++) {
@@ -1561,7 +1567,7 @@ extern "C" int gc_zstd_decompress_device(gc_ctx* c, const void* d_src, size_t n,
         } else if (!overlap) {
             hipEventRecord(c->evPart[1][3], c->stream);
             gc_zstd_dec_launch_exec(c->stream, (const uint8_t*)d_src, n, (uint8_t*)d_dst, dstCap, c->zdFrames, (uint32_t)cnt, c->zdBlocks, c->zdTicket,
-                                    c->zdLit, litTot + 64u, c->zdSeq, c->zdResult, zdProf, c->zdReady);
+                                    c->zdLit, litTot + 64u, c->zdSeq, c->zdResult, zdProf, c->zdReady, c->zdict, c->zdictSize);
             hipEventRecord(c->evPart[1][4], c->stream);
         } else {
             hipEventRecord(c->evPart[1][4], c->stream3);

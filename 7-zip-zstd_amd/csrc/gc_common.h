@@ -23,6 +23,7 @@
 #define GC_MIN_MATCH        5u               // shortest match the finder emits
 #define GC_MATCH_CAP        64u              // per-position compare cap; longer matches are chained + merged in K3
 #define GC_MAX_SEQ_PER_BLOCK (GC_ZSTD_BLOCK_MAX / GC_MIN_MATCH + 8u)
+#define GC_ZDICT_LOG        17u              // raw-content dictionaries: log2 of the entries of each of the two digest tables (one entry per dictionary byte at GC_ZSTD_DICT_MAX)
 
 // K1 -> K2/K3 interface, per block b (strides in elements):
 //   seqRaw[b * GC_MAX_SEQ_PER_BLOCK + i] = { litRank, (offset << 8) | matchLength }

@@ -130,7 +130,12 @@ extern "C" int gc_zstd_batch_compress_device(gc_ctx* c, const void* d_src, size_
         const gc_batch_item* rItems = dItems + i0;
         hipEvent_t* ev = c->btEv + (size_t)r * GC_BT_EVENTS;
         HIPCHK(c, hipEventRecord(ev[0], c->stream));
-        GC_LAUNCH(gc_zstd_lz_batch_kernel, m, 1024, c->stream, src, rItems, (GcSeqRaw*)c->seqRaw, (uint8_t*)c->lit, (GcBlockMeta*)c->meta);
+        if (c->zdictSize) {      // K1b's dictionary variant: the context's dictionary as history in front of every item
+            GC_LAUNCH(gc_zstd_lz_batch_dict_kernel, m, 1024, c->stream, src, rItems, (GcSeqRaw*)c->seqRaw, (uint8_t*)c->lit, (GcBlockMeta*)c->meta,
+                      (const uint8_t*)c->zdict, c->zdictSize, (const uint32_t*)c->zdictTabL, (const uint32_t*)c->zdictTabS);
+        } else {
+            GC_LAUNCH(gc_zstd_lz_batch_kernel, m, 1024, c->stream, src, rItems, (GcSeqRaw*)c->seqRaw, (uint8_t*)c->lit, (GcBlockMeta*)c->meta);
+        }
         HIPCHK(c, hipEventRecord(ev[1], c->stream));
         HIPCHK(c, hipStreamWaitEvent(c->stream2, ev[1], 0));
         HIPCHK(c, hipStreamWaitEvent(c->stream3, ev[1], 0));
@@ -226,5 +231,43 @@ extern "C" int gc_zstd_batch_timing(gc_ctx* c, float ms[4])
         HIPCHK(c, hipEventElapsedTime(&t, ev[4], ev[5])); ms[2] += t;
     }
     HIPCHK(c, hipEventElapsedTime(&ms[3], c->btEvCall[0], c->btEvCall[2]));
+    return GC_OK;
+}
+
+// ---- raw-content dictionaries (gpucodec.h "ZSTD, dictionaries"; DESIGN.md section 4 "Dictionaries") ----
+#define GC_ZDICT_PAD 32u                     // zero bytes behind the dictionary: a 16-byte compare window that starts at its last byte stays inside the allocation
+#define GC_ZDICT_TAB_BYTES ((size_t)4u << GC_ZDICT_LOG)     // one digest table of K1b's dictionary variant (gc_zstd_lz.hip)
+
+extern "C" size_t gc_zstd_dictionary_size(gc_ctx* c) { return c ? c->zdictSize : 0u; }
+
+extern "C" int gc_zstd_set_dictionary(gc_ctx* c, const void* dict, size_t n)
+{
+    if (!c) return GC_ERR_PARAM;
+    if (n && !dict) { snprintf(c->err, sizeof(c->err), "dictionary: null pointer with %zu bytes", n); return GC_ERR_PARAM; }
+    if (n && n < 8u) { snprintf(c->err, sizeof(c->err), "dictionary of %zu bytes: fewer than 8 bytes cannot be matched against (libzstd would ignore it)", n); return GC_ERR_PARAM; }
+    if (n > GC_ZSTD_DICT_MAX) { snprintf(c->err, sizeof(c->err), "dictionary of %zu bytes: more than GC_ZSTD_DICT_MAX (%u)", n, GC_ZSTD_DICT_MAX); return GC_ERR_PARAM; }
+    if (n) {
+        const uint8_t* d = (const uint8_t*)dict;
+        const uint32_t magic = (uint32_t)d[0] | ((uint32_t)d[1] << 8) | ((uint32_t)d[2] << 16) | ((uint32_t)d[3] << 24);
+        if (magic == 0xEC30A437u) { snprintf(c->err, sizeof(c->err), "formatted dictionary (magic 0xEC30A437): only raw-content dictionaries are supported"); return GC_ERR_UNSUPPORTED; }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    // whatever is in flight finishes with the dictionary it was started with
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream2));
+    HIPCHK(c, hipStreamSynchronize(c->stream3));
+    if (c->streamHash) HIPCHK(c, hipStreamSynchronize(c->streamHash));
+    c->zdictSize = 0;
+    if (!n) return GC_OK;
+    if (gc_buf_reserve(c->zdict, GC_ZSTD_DICT_MAX + GC_ZDICT_PAD) != GC_OK || gc_buf_reserve(c->zdictTabL, GC_ZDICT_TAB_BYTES) != GC_OK ||
+        gc_buf_reserve(c->zdictTabS, GC_ZDICT_TAB_BYTES) != GC_OK) { snprintf(c->err, sizeof(c->err), "dictionary: no device memory"); return GC_ERR_NOMEM; }
+    HIPCHK(c, hipMemsetAsync(c->zdict, 0, GC_ZSTD_DICT_MAX + GC_ZDICT_PAD, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->zdictTabL, 0, GC_ZDICT_TAB_BYTES, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->zdictTabS, 0, GC_ZDICT_TAB_BYTES, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->zdict, dict, n, hipMemcpyHostToDevice, c->stream));
+    GC_LAUNCH(gc_zstd_dict_digest_kernel, ((uint32_t)n + 255u) / 256u, 256, c->stream, (const uint8_t*)c->zdict, (uint32_t)n, (uint32_t*)c->zdictTabL, (uint32_t*)c->zdictTabS);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (`dict` is the caller's again; the tables are read-only from here on)
+    c->zdictSize = (uint32_t)n;
     return GC_OK;
 }

@@ -30,7 +30,9 @@
 //   NCount, FSE decoding tables        FSE_readNCount_body entropy_common.c:42, ZSTD_buildFSETable_body zstd_decompress_block.c:485
 //   sequences header / decode / exec   ZSTD_decodeSeqHeaders :695, ZSTD_decodeSequence :1229, ZSTD_execSequence :1001
 //   content checksum                   XXH64 (xxhash.h), zstd_decompress.c:1034-1056
-// Not supported: dictionaries (a frame with a dictionary id is refused), legacy (v0.x) frames, offsets of 2 GiB and more.
+// Not supported: formatted dictionaries and dictionary ids (a frame with a dictionary id is refused), legacy (v0.x) frames, offsets of 2 GiB and more.
+// A raw-content dictionary of the context (gc_zstd_set_dictionary; DESIGN.md section 4 "Dictionaries") lies as history in front of every frame: offsets up to
+// produced + dictSize are sound, and a match byte whose source lies in front of the frame is a literal from the dictionary's buffer (dict == nullptr, dictSize 0: none).
 #include "gpucodec.h"
 #include "gc_zstd_dec.h"
 #include "gc_device.h"
@@ -998,7 +1000,7 @@ enum { XV_ERR = 0, XV_FRAME, XV_REP0, XV_REP1, XV_REP2, XV_COUNT };
 extern "C" __global__ void __launch_bounds__(GC_ZD_T)
 gc_zstd_dec_exec_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, uint8_t* dst, uint64_t dstCap, const GcZdFrame* __restrict__ frames, uint32_t nFrames,
                         const GcZdBlock* blocks, uint32_t* ticket, const uint8_t* litWork, uint64_t litWorkSize, GcU4* seqWork, uint64_t* result,
-                        unsigned long long* prof, const uint32_t* ready)
+                        unsigned long long* prof, const uint32_t* ready, const uint8_t* __restrict__ dict, uint32_t dictSize)
 {
     __shared__ __attribute__((aligned(16))) uint8_t sOut[GC_ZSTD_BLOCK_MAX + 32u];
     __shared__ uint32_t sV[XV_COUNT];
@@ -1073,10 +1075,17 @@ gc_zstd_dec_exec_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, uint8
                         off = in - delta; rec.z = off; seq[j] = rec;
                     }
                     const uint32_t d = dp + ll;
-                    if ((uint64_t)off > produced + d) { bad = 1; continue; }
+                    if ((uint64_t)off > produced + d + dictSize) { bad = 1; continue; }
                     if (lt == 1u) for (uint32_t k = 0; k < ll; k++) sOut[dp + k] = rleByte;
                     else zd_copy_in(sOut + dp, litSrc + lp, ll, litLimit);
-                    if (off >= d + ml) zd_copy_in(sOut + d, bdst + d - off, ml, bdst);      // the whole source lies in front of the block
+                    uint32_t nd = 0;                                   // bytes of the source that lie in front of the frame: in the dictionary
+                    if ((uint64_t)off > produced + d) {
+                        const uint32_t back = (uint32_t)((uint64_t)off - produced - d);      // (1 .. dictSize)
+                        nd = back < ml ? back : ml;
+                        const uint8_t* const ds = dict + (dictSize - back);
+                        for (uint32_t k = 0; k < nd; k++) sOut[d + k] = ds[k];
+                    }
+                    if (off >= d + ml) zd_copy_in(sOut + d + nd, bdst + d + nd - off, ml - nd, bdst);      // the whole source (behind its dictionary part) lies in front of the block
                 }
                 {
                     const uint32_t lp = e.lposEnd, dp = e.dposEnd, rest = e.regen - lp;
@@ -1104,6 +1113,11 @@ gc_zstd_dec_exec_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, uint8
                         // what is left of my match: output position, length, distance.  A lane copies at most 16 bytes per round (so that one
                         // long match does not hold up the round); what remains is the same kind of match further on.
                         uint32_t d = mine.w + ll, ml = ml0, off = off0;
+                        if ((uint64_t)off > produced + d) {            // the part of the source in the dictionary was copied by pass 1: what is left is the same match further on
+                            const uint64_t back = (uint64_t)off - produced - d;
+                            const uint32_t nd = back < ml ? (uint32_t)back : ml;
+                            d += nd; ml -= nd;
+                        }
                         bool pending = have && off < d + ml;
                         // matches the lane-parallel path does not take: long ones, periods below 8 bytes, sources that start in front of the block.
                         // They wait until they are first, then the whole wave copies them (64 bytes per step).
@@ -1305,10 +1319,18 @@ gc_zstd_dec_place_kernel(const GcZdFrame* __restrict__ frames, uint32_t nFrames,
     if (lane == 0) { result[f] = produced | ((uint64_t)status << 56); ferr[f] = 0; }
 }
 
+// how many of a match's ml source bytes lie in front of the frame (in the dictionary): the match is written at frame position `at` with offset off
+__device__ __forceinline__ uint32_t zw_dict_part(uint32_t off, uint64_t at, uint32_t ml)
+{
+    if ((uint64_t)off <= at) return 0u;
+    const uint64_t back = (uint64_t)off - at;
+    return back < ml ? (uint32_t)back : ml;
+}
+
 extern "C" __global__ void __launch_bounds__(256)
 gc_zstd_dec_spread_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, uint8_t* __restrict__ dst, const GcZdFrame* __restrict__ frames, const GcZdBlock* __restrict__ blocks,
                           const GcZdPlace* __restrict__ place, const uint8_t* __restrict__ litWork, uint64_t litWorkSize, const GcU4* __restrict__ seqWork,
-                          uint32_t* __restrict__ ptr, uint64_t batchBase, uint32_t* __restrict__ ferr)
+                          uint32_t* __restrict__ ptr, uint64_t batchBase, uint32_t* __restrict__ ferr, const uint8_t* __restrict__ dict, uint32_t dictSize)
 {
     __shared__ uint32_t sList[256];
     __shared__ uint32_t sCount;
@@ -1343,13 +1365,15 @@ gc_zstd_dec_spread_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, uin
                 if (in <= delta) ok = false; else off = in - delta;
             }
             const uint32_t d = dp + ll;
-            if (ok && (uint64_t)off > pl.dst + d) ok = false;
+            if (ok && (uint64_t)off > pl.dst + d + dictSize) ok = false;
             if (!ok) bad = 1;
             else if (ll > GC_ZW_LANE_MAX || ml > GC_ZW_LANE_MAX) sList[atomicAdd(&sCount, 1u)] = j;
             else {
                 for (uint32_t k = 0; k < ll; k++) { const uint8_t v = lt == 1u ? rleByte : litSrc[lp + k]; bdst[dp + k] = v; bptr[dp + k] = GC_ZW_FINAL | v; }
                 const uint32_t q0 = P + d - off;
-                for (uint32_t k = 0; k < ml; k++) bptr[d + k] = q0 + k;
+                const uint32_t nd = zw_dict_part(off, pl.dst + d, ml);             // source bytes in front of the frame: final at once, from the dictionary
+                for (uint32_t k = 0; k < nd; k++) { const uint8_t v = dict[dictSize - (uint32_t)((uint64_t)off - pl.dst - d) + k]; bdst[d + k] = v; bptr[d + k] = GC_ZW_FINAL | v; }
+                for (uint32_t k = nd; k < ml; k++) bptr[d + k] = q0 + k;
             }
         }
         __syncthreads();
@@ -1360,8 +1384,12 @@ gc_zstd_dec_spread_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, uin
             uint32_t off = rec.z;
             if (off & GC_ZD_SYM) { const uint32_t k = off & 3u, delta = (off & 0x7FFFFFFFu) >> 2; off = pl.rep[k == 0u ? 0 : (k == 1u ? 1 : 2)] - delta; }
             const uint32_t d = dp + ll, q0 = P + d - off;
+            const uint32_t nd = zw_dict_part(off, pl.dst + d, ml);
             for (uint32_t k = t; k < ll; k += 256u) { const uint8_t v = lt == 1u ? rleByte : litSrc[lp + k]; bdst[dp + k] = v; bptr[dp + k] = GC_ZW_FINAL | v; }
-            for (uint32_t k = t; k < ml; k += 256u) bptr[d + k] = q0 + k;
+            for (uint32_t k = t; k < ml; k += 256u) {
+                if (k < nd) { const uint8_t v = dict[dictSize - (uint32_t)((uint64_t)off - pl.dst - d) + k]; bdst[d + k] = v; bptr[d + k] = GC_ZW_FINAL | v; }
+                else bptr[d + k] = q0 + k;
+            }
         }
         __syncthreads();
     }
@@ -1484,7 +1512,7 @@ static int zd_scan(const uint8_t* src, size_t n, gc_zstd_frame* out, size_t maxF
         uint32_t did = 0;
         for (uint32_t i = 0; i < didSize; i++) did |= (uint32_t)src[p + i] << (8u * i);
         p += didSize;
-        if (did) return GC_ERR_PARAM;                                  // dictionaries are not supported
+        if (did) return GC_ERR_PARAM;                                  // dictionary ids (formatted dictionaries) are not supported; a raw-content dictionary has none
         uint64_t fcs = 0;
         for (uint32_t i = 0; i < fcsSize; i++) fcs |= (uint64_t)src[p + i] << (8u * i);
         if (fcsSize == 2u) fcs += 256u;
@@ -1554,10 +1582,10 @@ extern "C" void gc_zstd_dec_launch_sequences(hipStream_t st, const uint8_t* src,
 }
 extern "C" void gc_zstd_dec_launch_exec(hipStream_t st, const uint8_t* src, uint64_t srcSize, uint8_t* dst, uint64_t dstCap, const GcZdFrame* frames, uint32_t nFrames,
                                         GcZdBlock* blocks, uint32_t* ticket, uint8_t* litWork, uint64_t litWorkSize, void* seqWork, uint64_t* result, unsigned long long* prof,
-                                        const uint32_t* ready)
+                                        const uint32_t* ready, const uint8_t* dict, uint32_t dictSize)
 {
     const uint32_t wg = nFrames < GC_ZD_MAX_WG ? nFrames : GC_ZD_MAX_WG;
-    GC_LAUNCH(gc_zstd_dec_exec_kernel, wg, GC_ZD_T, st, src, srcSize, dst, dstCap, frames, nFrames, (const GcZdBlock*)blocks, ticket, (const uint8_t*)litWork, litWorkSize, (GcU4*)seqWork, result, prof, ready);
+    GC_LAUNCH(gc_zstd_dec_exec_kernel, wg, GC_ZD_T, st, src, srcSize, dst, dstCap, frames, nFrames, (const GcZdBlock*)blocks, ticket, (const uint8_t*)litWork, litWorkSize, (GcU4*)seqWork, result, prof, ready, dict, dictSize);
 }
 
 // ---- wide execution (all blocks of all frames at once; see the kernels) ----
@@ -1566,9 +1594,10 @@ extern "C" void gc_zstd_dec_launch_place(hipStream_t st, const GcZdFrame* frames
     if (nFrames) GC_LAUNCH(gc_zstd_dec_place_kernel, nFrames, 64, st, frames, nFrames, blocks, dstCap, place, result, ferr);
 }
 extern "C" void gc_zstd_dec_launch_spread(hipStream_t st, const uint8_t* src, uint64_t srcSize, uint8_t* dst, const GcZdFrame* frames, const GcZdBlock* blocks, uint32_t nBlocks,
-                                          const GcZdPlace* place, const uint8_t* litWork, uint64_t litWorkSize, const void* seqWork, uint32_t* ptr, uint64_t batchBase, uint32_t* ferr)
+                                          const GcZdPlace* place, const uint8_t* litWork, uint64_t litWorkSize, const void* seqWork, uint32_t* ptr, uint64_t batchBase, uint32_t* ferr,
+                                          const uint8_t* dict, uint32_t dictSize)
 {
-    if (nBlocks) GC_LAUNCH(gc_zstd_dec_spread_kernel, nBlocks, 256, st, src, srcSize, dst, frames, blocks, place, litWork, litWorkSize, (const GcU4*)seqWork, ptr, batchBase, ferr);
+    if (nBlocks) GC_LAUNCH(gc_zstd_dec_spread_kernel, nBlocks, 256, st, src, srcSize, dst, frames, blocks, place, litWork, litWorkSize, (const GcU4*)seqWork, ptr, batchBase, ferr, dict, dictSize);
 }
 extern "C" void gc_zstd_dec_launch_chase(hipStream_t st, uint8_t* dstBatch, uint32_t* ptr, uint32_t n, uint32_t hops, uint8_t* pieceDone, uint32_t* counter)
 {

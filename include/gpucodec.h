@@ -246,6 +246,28 @@ int         gc_zstd_batch_timing(gc_ctx* ctx, float ms[4]);
 /* items per round of this context's batch calls (DESIGN.md section 4 "Batches": what the workspace budget holds; 0 without a context) */
 size_t      gc_zstd_batch_round_items(gc_ctx* ctx);
 
+/* ---- ZSTD, dictionaries: a RAW-CONTENT dictionary for the batch encoder and the decoder (ZSTD_compress_usingDict / ZSTD_decompress_usingDict with bytes that do
+ * not start with the dictionary magic).  The dictionary is history that lies immediately in front of every item / frame: matches may reach into it, offsets run up
+ * to dictSize + position, and no dictionary id is written (a raw dictionary has id 0).  On small items -- where a frame that knows only its own bytes compresses
+ * poorly -- this is most of the ratio; both sides must hold the same bytes.
+ *   gc_zstd_set_dictionary(ctx, dict, n): `dict` is host memory; the bytes are copied to the device and digested there once (two hash tables over every position,
+ *   read-only from then on).  n == 0 removes the dictionary.  The call first synchronises the context's streams: a pending batch call finishes with the dictionary it
+ *   was started with.  Accepted: 8 <= n <= GC_ZSTD_DICT_MAX.  Refused, each with a message (gc_last_error_message), the dictionary in place staying as it was:
+ *     1 .. 7 bytes                      GC_ERR_PARAM        (libzstd's compressor silently ignores such a dictionary; refused here instead of guessed)
+ *     more than GC_ZSTD_DICT_MAX        GC_ERR_PARAM
+ *     first four bytes 0xEC30A437       GC_ERR_UNSUPPORTED  raw content only: a formatted dictionary (entropy tables, repeat offsets, an id) is refused, not misread
+ *   Encoder: while a dictionary is set, gc_zstd_batch_compress_device / _host code every item against it (the same dictionary for every item of the call).  The frames
+ *   keep their header (single segment, content size, no dictionary id), the raw-block fallback, the checksum option -- the checksum covers the item alone -- and the
+ *   packing; the repeat offsets start at 1, 4, 8 and are usable from position 0.  The output is deterministic: the same bytes on every run and for every round size,
+ *   identical items give identical frames.  Without a dictionary the batch calls write byte for byte what they always wrote.  The STREAM calls (gc_zstd_compress_*,
+ *   gc_codec_compress_* / gc_host_begin* with GC_CODEC_ZSTD) on a context that holds a dictionary return GC_ERR_UNSUPPORTED: they are never silently dictionary-less.
+ *   Decoder: while a dictionary is set, gc_zstd_decompress_device / _host accept offsets up to produced + dictSize at every position of every frame (the rule of the
+ *   reference's one-shot call; the window descriptor does not enter), the bytes in front of the frame coming from the dictionary.  A frame with a nonzero dictionary
+ *   id is still refused (GC_ERR_PARAM); a frame that never reaches in front of itself decodes the same with and without a dictionary. */
+#define GC_ZSTD_DICT_MAX (128u << 10)
+int         gc_zstd_set_dictionary(gc_ctx* ctx, const void* dict, size_t n);
+size_t      gc_zstd_dictionary_size(gc_ctx* ctx);
+
 /* ---- CRC-32 of data that lies in device memory (C/7zCrc.c CrcCalc: polynomial 0xEDB88320, init and final XOR 0xFFFFFFFF).
  * Synchronous, on the current device's default stream. */
 int         gc_crc32_device(const void* d_src, size_t n, uint32_t* crc);
