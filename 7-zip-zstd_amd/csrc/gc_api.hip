@@ -791,6 +791,50 @@ extern "C" int gc_mf_pass_timing(gc_ctx* c, float ms[4])
     return GC_OK;
 }
 
+// The entropy stage of the zstd stream call, shared with the test entry gc_test_zstd_encode_parsed (below) so that what the tests feed an exact parse runs the product's
+// launches and nothing else.  zstd_entropy_part: K3a-d on stream2 and K2 on stream3 over the blocks blk0 .. blk0 + pBlocks of one part (len content bytes), behind
+// evPart[p][0] (recorded on the main stream where that part's raw sequences, literals and block metas are complete).
+static int zstd_entropy_part(gc_ctx* c, uint32_t p, uint32_t blk0, uint32_t pBlocks, size_t len, uint32_t zFrameBlocks)
+{
+    // K2 (literals) and K3 (sequences) are independent consumers of the finder: two more streams
+    HIPCHK(c, hipStreamWaitEvent(c->stream2, c->evPart[p][0], 0));
+    HIPCHK(c, hipStreamWaitEvent(c->stream3, c->evPart[p][0], 0));
+    if (p == 0u) HIPCHK(c, hipEventRecord(c->ev[3], c->stream2));
+    {   // K3: codes -> tables -> state chains -> pack (gc_zstd_seq.hip)
+        unsigned long long* sprof = c->profOn ? c->prof + GC_LZ_PHASES : nullptr;
+        uint8_t* codes = c->codes + (size_t)blk0 * 3u * GC_MAX_SEQ_PER_BLOCK;
+        uint64_t* packed = c->seqPacked + (size_t)blk0 * GC_MAX_SEQ_PER_BLOCK;
+        uint16_t* st = c->stOut + (size_t)blk0 * 3u * GC_SEQ_ST_STRIDE;
+        GC_LAUNCH(gc_zstd_seq_codes_kernel, pBlocks, GC_SEQ_T, c->stream2, (const GcSeqRaw*)(c->seqRaw + (size_t)blk0 * GC_MAX_SEQ_PER_BLOCK), (const GcBlockMeta*)(c->meta + blk0),
+                  packed, c->seqOff + (size_t)blk0 * GC_MAX_SEQ_PER_BLOCK, codes, c->seqHist + blk0, c->seqSec + (size_t)blk0 * GC_SEQSEC_STRIDE, c->info + blk0, zFrameBlocks, sprof);
+        GC_LAUNCH(gc_zstd_seq_tables_kernel, pBlocks * 3u, 64, c->stream2, (const GcSeqHist*)(c->seqHist + blk0), (const GcSectionInfo*)(c->info + blk0), c->seqTabs + (size_t)blk0 * 3u, sprof);
+        GC_LAUNCH(gc_zstd_seq_chain_kernel, pBlocks * 3u, 64, c->stream2, (const uint8_t*)codes, (const GcSectionInfo*)(c->info + blk0), c->seqTabs + (size_t)blk0 * 3u, st, sprof);
+        GC_LAUNCH(gc_zstd_seq_pack_kernel, pBlocks, GC_SEQ_T, c->stream2, (const uint64_t*)packed, (const uint8_t*)codes, (const uint16_t*)st, (const GcSeqTabG*)(c->seqTabs + (size_t)blk0 * 3u),
+                  c->seqSec + (size_t)blk0 * GC_SEQSEC_STRIDE, c->info + blk0, (uint64_t)len, sprof);
+    }
+    GC_LAUNCH(gc_zstd_huf_kernel, pBlocks, 256, c->stream3, (const uint8_t*)(c->lit + (size_t)blk0 * GC_ZSTD_BLOCK_MAX), (const GcBlockMeta*)(c->meta + blk0),
+              c->litSec + (size_t)blk0 * GC_LITSEC_STRIDE, c->info + blk0);
+    return GC_OK;
+}
+
+// ... and what follows the last part: both streams join the main one (K0x too where it ran), K4 plans the frames, K5 writes them
+static int zstd_join_and_emit(gc_ctx* c, const uint8_t* src, size_t n, void* d_dst, size_t dstCap, uint32_t nBlocks, uint32_t zFrameBlocks)
+{
+    HIPCHK(c, hipEventRecord(c->ev[4], c->stream2));
+    HIPCHK(c, hipEventRecord(c->ev[2], c->stream3));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev[2], 0));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev[4], 0));
+    if (c->hashTimed) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evHash[1], 0));                // K0x joins in front of K4 / K5
+    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+    GC_LAUNCH(gc_zstd_plan_kernel, 1, 1024, c->stream, (const GcSectionInfo*)c->info, nBlocks, (uint64_t)n, (uint64_t)dstCap, zFrameBlocks, c->plan, c->result, c->optSeekTable, c->optChecksum);
+    HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
+    GC_LAUNCH(gc_zstd_emit_kernel, nBlocks + (c->optSeekTable ? 1u : 0u), 256, c->stream, src, (uint64_t)n, (const uint8_t*)c->litSec, (const uint8_t*)c->seqSec,
+              (const GcSectionInfo*)c->info, (const GcFramePlan*)c->plan, (const uint64_t*)c->result, nBlocks, zFrameBlocks, (uint8_t*)d_dst,
+              c->optChecksum ? (const uint64_t*)c->xxh : nullptr);
+    HIPCHK(c, hipEventRecord(c->ev[7], c->stream));
+    return GC_OK;
+}
+
 extern "C" int gc_zstd_compress_device(gc_ctx* c, const void* d_src, size_t n, void* d_dst, size_t dstCap, int level)
 {
     if (!c || (!d_src && n) || !d_dst) return GC_ERR_PARAM;
@@ -865,43 +909,82 @@ extern "C" int gc_zstd_compress_device(gc_ctx* c, const void* d_src, size_t n, v
         if (rc != GC_OK) return rc;
         HIPCHK(c, hipEventRecord(c->evPart[p][0], c->stream));                                 // finder of this part done
         if (p + 1u == nParts || blk0 + pBlocks >= nBlocks) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-        // K2 (literals) and K3 (sequences) are independent consumers of the finder: two more streams
-        HIPCHK(c, hipStreamWaitEvent(c->stream2, c->evPart[p][0], 0));
-        HIPCHK(c, hipStreamWaitEvent(c->stream3, c->evPart[p][0], 0));
-        if (p == 0u) HIPCHK(c, hipEventRecord(c->ev[3], c->stream2));
-        {   // K3: codes -> tables -> state chains -> pack (gc_zstd_seq.hip)
-            unsigned long long* sprof = c->profOn ? c->prof + GC_LZ_PHASES : nullptr;
-            uint8_t* codes = c->codes + (size_t)blk0 * 3u * GC_MAX_SEQ_PER_BLOCK;
-            uint64_t* packed = c->seqPacked + (size_t)blk0 * GC_MAX_SEQ_PER_BLOCK;
-            uint16_t* st = c->stOut + (size_t)blk0 * 3u * GC_SEQ_ST_STRIDE;
-            GC_LAUNCH(gc_zstd_seq_codes_kernel, pBlocks, GC_SEQ_T, c->stream2, (const GcSeqRaw*)(c->seqRaw + (size_t)blk0 * GC_MAX_SEQ_PER_BLOCK), (const GcBlockMeta*)(c->meta + blk0),
-                      packed, c->seqOff + (size_t)blk0 * GC_MAX_SEQ_PER_BLOCK, codes, c->seqHist + blk0, c->seqSec + (size_t)blk0 * GC_SEQSEC_STRIDE, c->info + blk0, zFrameBlocks, sprof);
-            GC_LAUNCH(gc_zstd_seq_tables_kernel, pBlocks * 3u, 64, c->stream2, (const GcSeqHist*)(c->seqHist + blk0), (const GcSectionInfo*)(c->info + blk0), c->seqTabs + (size_t)blk0 * 3u, sprof);
-            GC_LAUNCH(gc_zstd_seq_chain_kernel, pBlocks * 3u, 64, c->stream2, (const uint8_t*)codes, (const GcSectionInfo*)(c->info + blk0), c->seqTabs + (size_t)blk0 * 3u, st, sprof);
-            GC_LAUNCH(gc_zstd_seq_pack_kernel, pBlocks, GC_SEQ_T, c->stream2, (const uint64_t*)packed, (const uint8_t*)codes, (const uint16_t*)st, (const GcSeqTabG*)(c->seqTabs + (size_t)blk0 * 3u),
-                      c->seqSec + (size_t)blk0 * GC_SEQSEC_STRIDE, c->info + blk0, (uint64_t)len, sprof);
-        }
-        GC_LAUNCH(gc_zstd_huf_kernel, pBlocks, 256, c->stream3, (const uint8_t*)(c->lit + (size_t)blk0 * GC_ZSTD_BLOCK_MAX), (const GcBlockMeta*)(c->meta + blk0),
-                  c->litSec + (size_t)blk0 * GC_LITSEC_STRIDE, c->info + blk0);
+        rc = zstd_entropy_part(c, p, blk0, pBlocks, len, zFrameBlocks);
+        if (rc != GC_OK) return rc;
         usedParts = p + 1u;
     }
     c->mfTimed = MF_F(zArg) > 1u; c->mfParts = usedParts; c->mfPriced = c->mfTimed && plan.priceParse != 0u;
-    HIPCHK(c, hipEventRecord(c->ev[4], c->stream2));
-    HIPCHK(c, hipEventRecord(c->ev[2], c->stream3));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev[2], 0));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev[4], 0));
-    if (c->hashTimed) HIPCHK(c, hipStreamWaitEvent(c->stream, c->evHash[1], 0));                // K0x joins in front of K4 / K5
-    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
-    GC_LAUNCH(gc_zstd_plan_kernel, 1, 1024, c->stream, (const GcSectionInfo*)c->info, nBlocks, (uint64_t)n, (uint64_t)dstCap, zFrameBlocks, c->plan, c->result, c->optSeekTable, c->optChecksum);
-    HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
-    GC_LAUNCH(gc_zstd_emit_kernel, nBlocks + (c->optSeekTable ? 1u : 0u), 256, c->stream, src, (uint64_t)n, (const uint8_t*)c->litSec, (const uint8_t*)c->seqSec,
-              (const GcSectionInfo*)c->info, (const GcFramePlan*)c->plan, (const uint64_t*)c->result, nBlocks, zFrameBlocks, (uint8_t*)d_dst,
-              c->optChecksum ? (const uint64_t*)c->xxh : nullptr);
-    HIPCHK(c, hipEventRecord(c->ev[7], c->stream));
+    rc = zstd_join_and_emit(c, src, n, d_dst, dstCap, nBlocks, zFrameBlocks);
+    if (rc != GC_OK) return rc;
     HIPCHK(c, hipGetLastError());
     c->pending = true; c->timed = true; c->lastCodec = 0;
     return GC_OK;
 }
+
+#ifdef GC_TEST_HOOKS
+// Test entry (the test builds only; not part of include/gpucodec.h): the zstd stream call with the match finder replaced by a parse the caller states, so that a test
+// decides exactly which literals and sequences the entropy stage gets.  d_src / d_dst: device memory, as in gc_zstd_compress_device.  lit / seq / meta: HOST memory, what K1
+// leaves per block (gc_common.h), packed -- block b's literals follow block b - 1's, its records likewise, meta[b] counts both.  The frames are the level's
+// (lz_frame_arg; GC_FRAME_BLOCKS holds).  The parse is checked here, on the host, before anything is launched: a parse the kernels were not sized for, or one that
+// does not tile its block, or a match that reaches in front of its frame, is refused with GC_ERR_PARAM.  (That it REPRODUCES the input is the caller's business.)
+// gc_zstd_finish reads the result.
+extern "C" int gc_test_zstd_encode_parsed(gc_ctx* c, const void* d_src, size_t n, void* d_dst, size_t dstCap, int level,
+                                          const uint8_t* lit, const GcSeqRaw* seq, const GcBlockMeta* meta)
+{
+    if (!c || !d_src || !n || !d_dst || !meta) return GC_ERR_PARAM;
+    if (c->zdictSize || c->optChecksum) { snprintf(c->err, sizeof(c->err), "the parsed test entry takes no dictionary and writes no content checksums"); return GC_ERR_UNSUPPORTED; }
+    const uint32_t nBlocks = gc_num_blocks(n);
+    const uint32_t zFrameBlocks = MF_C(lz_frame_arg(GC_CODEC_ZSTD, level, nBlocks, c->dbgFrameBlocks));
+    size_t litTotal = 0, seqTotal = 0;
+    for (uint32_t b = 0; b < nBlocks; b++) {
+        const size_t base = (size_t)b * GC_ZSTD_BLOCK_MAX;
+        const uint32_t blockLen = (uint32_t)(n - base < GC_ZSTD_BLOCK_MAX ? n - base : GC_ZSTD_BLOCK_MAX);
+        const GcBlockMeta m = meta[b];
+        const char* bad = nullptr;
+        if (m.nSeqRaw > GC_MAX_SEQ_PER_BLOCK) bad = "more records than a block's workspace holds";
+        else if (m.nLit > blockLen) bad = "more literals than the block is long";
+        else if ((m.nLit && !lit) || (m.nSeqRaw && !seq)) bad = "counts without data";
+        uint64_t covered = m.nLit;                                         // literals + match lengths
+        const uint64_t inFrame = (uint64_t)(b % zFrameBlocks) * GC_ZSTD_BLOCK_MAX;      // content of the frame in front of the block
+        uint32_t prevRank = 0; uint64_t matched = 0;
+        for (uint32_t i = 0; !bad && i < m.nSeqRaw; i++) {
+            const GcSeqRaw r = seq[seqTotal + i];
+            const uint32_t ml = r.offml & 0xFFu, off = r.offml >> 8;
+            if (r.litRank < prevRank || r.litRank > m.nLit) bad = "litRank decreases or exceeds nLit";
+            else if (ml < 3u) bad = "a match shorter than 3";
+            else if (off == 0u || off > inFrame + r.litRank + matched) bad = "an offset that reaches in front of the frame";
+            prevRank = r.litRank; matched += ml; covered += ml;
+        }
+        if (!bad && covered != blockLen) bad = "literals and matches do not add up to the block's length";
+        if (bad) { snprintf(c->err, sizeof(c->err), "parsed block %u: %s", b, bad); return GC_ERR_PARAM; }
+        litTotal += m.nLit; seqTotal += m.nSeqRaw;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    c->timed = false;
+    int rc = ensure_workspace(c, nBlocks);
+    if (rc != GC_OK) return rc;
+    if (c->profOn) { HIPCHK(c, hipMemsetAsync(c->prof, 0, (GC_LZ_PHASES + GC_SEQ_PHASES) * sizeof(unsigned long long), c->stream)); c->profBlocks = nBlocks; }
+    HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+    c->hashTimed = false; c->mfTimed = false; c->mfParts = 0; c->mfPriced = false;
+    HIPCHK(c, hipMemcpyAsync(c->meta, meta, (size_t)nBlocks * sizeof(GcBlockMeta), hipMemcpyHostToDevice, c->stream));
+    litTotal = 0; seqTotal = 0;
+    for (uint32_t b = 0; b < nBlocks; b++) {       // K1's strides
+        if (meta[b].nLit) HIPCHK(c, hipMemcpyAsync(c->lit + (size_t)b * GC_ZSTD_BLOCK_MAX, lit + litTotal, meta[b].nLit, hipMemcpyHostToDevice, c->stream));
+        if (meta[b].nSeqRaw) HIPCHK(c, hipMemcpyAsync(c->seqRaw + (size_t)b * GC_MAX_SEQ_PER_BLOCK, seq + seqTotal, (size_t)meta[b].nSeqRaw * sizeof(GcSeqRaw), hipMemcpyHostToDevice, c->stream));
+        litTotal += meta[b].nLit; seqTotal += meta[b].nSeqRaw;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));                           // (the caller's buffers are pageable and his again when this returns)
+    HIPCHK(c, hipEventRecord(c->evPart[0][0], c->stream));
+    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+    rc = zstd_entropy_part(c, 0, 0, nBlocks, n, zFrameBlocks);
+    if (rc != GC_OK) return rc;
+    rc = zstd_join_and_emit(c, (const uint8_t*)d_src, n, d_dst, dstCap, nBlocks, zFrameBlocks);
+    if (rc != GC_OK) return rc;
+    HIPCHK(c, hipGetLastError());
+    c->pending = true; c->timed = true; c->lastCodec = 0;
+    return GC_OK;
+}
+#endif
 
 extern "C" int gc_zstd_finish(gc_ctx* c, size_t* compressedSize)
 {
