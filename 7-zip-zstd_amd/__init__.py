@@ -887,6 +887,23 @@ class ZstdEncoder(_ZstdDictionary, _EncoderBase):
         rec = np.ascontiguousarray(np.concatenate(recs + [np.zeros((1, 2), np.uint32)]))
         self._check(fn(self._ctx, d_src_ptr, n, d_dst_ptr, dst_cap, self.level, lit.ctypes.data, rec.ctypes.data, meta.ctypes.data), "gc_test_zstd_encode_parsed")
 
+    def wave_scans(self, v, keys):
+        """TEST BUILDS ONLY: the DPP wave scans of csrc/gc_device.h (gc_api.hip gc_test_wave_scans) on uint32 values v and uint64 keys of the same length, one
+        wave per 64 of them (the last wave is filled with zeros) -> (inclusive sums mod 2^32, inclusive maxima, inclusive maxima of the keys), per wave."""
+        import numpy as np
+        fn = getattr(self._lib, "gc_test_wave_scans", None)
+        if fn is None:
+            raise GpuCodecError("gc_test_wave_scans: this library is not a test build")
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        fn.restype = C.c_int
+        n = int(np.size(v))
+        m = (n + 63) // 64 * 64
+        vv, kk = np.zeros(m, np.uint32), np.zeros(m, np.uint64)
+        vv[:n], kk[:n] = np.asarray(v, dtype=np.uint32).ravel(), np.asarray(keys, dtype=np.uint64).ravel()
+        s, mx, mx64 = np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m, np.uint64)
+        self._check(fn(self._ctx, vv.ctypes.data, kk.ctypes.data, m, s.ctypes.data, mx.ctypes.data, mx64.ctypes.data), "gc_test_wave_scans")
+        return s[:n], mx[:n], mx64[:n]
+
     # ---- batches: many independent inputs of at most BATCH_ITEM_MAX bytes, one frame each, in one launch set (include/gpucodec.h "ZSTD, batched")
     BATCH_ITEM_MAX = 128 << 10
     BATCH_KERNELS = ("lz", "entropy", "frame", "total")

@@ -42,6 +42,7 @@ extern "C" __global__ void gc_zstd_seq_codes_kernel(const GcSeqRaw*, const GcBlo
 extern "C" __global__ void gc_zstd_seq_tables_kernel(const GcSeqHist*, const GcSectionInfo*, GcSeqTabG*, unsigned long long*);
 extern "C" __global__ void gc_zstd_seq_chain_kernel(const uint8_t*, const GcSectionInfo*, GcSeqTabG*, uint16_t*, unsigned long long*);
 extern "C" __global__ void gc_zstd_seq_pack_kernel(const uint64_t*, const uint8_t*, const uint16_t*, const GcSeqTabG*, uint8_t*, GcSectionInfo*, uint64_t, unsigned long long*);
+extern "C" __global__ void gc_wave_scan_test_kernel(const uint32_t*, const uint64_t*, uint32_t*, uint32_t*, uint64_t*);      // (gc_zstd_seq.hip; launched by gc_test_wave_scans only)
 extern "C" __global__ void gc_zstd_plan_kernel(const GcSectionInfo*, uint32_t, uint64_t, uint64_t, uint32_t, GcFramePlan*, uint64_t*, uint32_t, uint32_t);
 extern "C" __global__ void gc_zstd_emit_kernel(const uint8_t*, uint64_t, const uint8_t*, const uint8_t*, const GcSectionInfo*,
                                                const GcFramePlan*, const uint64_t*, uint32_t, uint32_t, uint8_t*, const uint64_t*);
@@ -982,6 +983,31 @@ extern "C" int gc_test_zstd_encode_parsed(gc_ctx* c, const void* d_src, size_t n
     if (rc != GC_OK) return rc;
     HIPCHK(c, hipGetLastError());
     c->pending = true; c->timed = true; c->lastCodec = 0;
+    return GC_OK;
+}
+
+// Test entry (the test builds only): the DPP wave scans of gc_device.h on a caller's values, one wave per 64 of them (n a multiple of 64).  HOST memory throughout:
+// sum[i] / mx[i] = inclusive sum (mod 2^32) / inclusive maximum of v over the lanes of i's wave up to i, mx64[i] the same maximum of the 64-bit keys.
+extern "C" int gc_test_wave_scans(gc_ctx* c, const uint32_t* v, const uint64_t* keys, size_t n, uint32_t* sum, uint32_t* mx, uint64_t* mx64)
+{
+    if (!c || !v || !keys || !sum || !mx || !mx64 || !n || (n & 63u) || n > (1u << 24)) return GC_ERR_PARAM;
+    HIPCHK(c, hipSetDevice(c->device));
+    void* d = nullptr;
+    HIPCHK(c, hipMalloc(&d, n * 32u));
+    uint64_t* const dKeys = (uint64_t*)d; uint64_t* const dMx64 = dKeys + n;               // the 8-byte arrays first: everything stays aligned
+    uint32_t* const dV = (uint32_t*)(dMx64 + n); uint32_t* const dSum = dV + n; uint32_t* const dMx = dSum + n;
+    hipError_t e = hipMemcpy(dV, v, n * 4u, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dKeys, keys, n * 8u, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        GC_LAUNCH(gc_wave_scan_test_kernel, (uint32_t)(n / 64u), 64, c->stream, (const uint32_t*)dV, (const uint64_t*)dKeys, dSum, dMx, dMx64);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(sum, dSum, n * 4u, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(mx, dMx, n * 4u, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(mx64, dMx64, n * 8u, hipMemcpyDeviceToHost);
+    hipFree(d);
+    if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "gc_test_wave_scans failed: %s", hipGetErrorString(e)); return GC_ERR_HIP; }
     return GC_OK;
 }
 #endif

@@ -199,6 +199,72 @@ __device__ __forceinline__ uint32_t gc_wave_max(uint32_t v)
     return v;
 }
 
+// The same three scans without the LDS crossbar: four row shifts inside the rows of 16 lanes, then the last lane of a row broadcast into the next row (rows 1
+// and 3), then lane 31 into the upper half -- six dependent DPP moves, where the shuffle loops above are six ds_bpermute_b32 round trips.  A lane a move does not
+// reach keeps `old`, the operation's identity.  Every move's result passes through an empty asm: this compiler's DPP combiner folds a DPP move into the
+// instruction that uses it, and the MI355X has read 0 through such a folded operand (profiles/r02_dpp_combine.md).  Under the emulator they ARE the loops above.
+#ifndef HIPEMU
+template <int CTRL, int ROWS> __device__ __forceinline__ uint32_t gc_dpp_mov(uint32_t old, uint32_t v)
+{
+    uint32_t r = (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, CTRL, ROWS, 0xF, false);
+    asm volatile("" : "+v"(r));
+    return r;
+}
+#define GC_DPP_SCAN_STEPS(STEP) STEP(0x111, 0xF) STEP(0x112, 0xF) STEP(0x114, 0xF) STEP(0x118, 0xF) STEP(0x142, 0xA) STEP(0x143, 0xC)   /* row_shr:1,2,4,8; row_bcast:15 into rows 1, 3; row_bcast:31 into rows 2, 3 */
+#endif
+__device__ __forceinline__ uint32_t gc_wave_incl_sum_dpp(uint32_t v)
+{
+#ifdef HIPEMU
+    return gc_wave_incl_sum(v);
+#else
+#define GC_STEP(C, M) v += gc_dpp_mov<C, M>(0u, v);
+    GC_DPP_SCAN_STEPS(GC_STEP)
+#undef GC_STEP
+    return v;
+#endif
+}
+__device__ __forceinline__ uint32_t gc_wave_incl_max_dpp(uint32_t v)
+{
+#ifdef HIPEMU
+    return gc_wave_incl_max(v);
+#else
+#define GC_STEP(C, M) { const uint32_t o = gc_dpp_mov<C, M>(0u, v); v = v > o ? v : o; }
+    GC_DPP_SCAN_STEPS(GC_STEP)
+#undef GC_STEP
+    return v;
+#endif
+}
+// inclusive max of 64-bit keys, carried as two 32-bit halves (a DPP move is 32 bits wide)
+__device__ __forceinline__ uint64_t gc_wave_incl_max64_dpp(uint64_t v)
+{
+#ifdef HIPEMU
+    const uint32_t lane = __lane_id() & 63u;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t lo = __shfl_up((uint32_t)v, d), hi = __shfl_up((uint32_t)(v >> 32), d);
+        const uint64_t o = ((uint64_t)hi << 32) | lo;
+        if (lane >= (uint32_t)d && o > v) v = o;
+    }
+    return v;
+#else
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+#define GC_STEP(C, M) { const uint32_t ol = gc_dpp_mov<C, M>(0u, lo), oh = gc_dpp_mov<C, M>(0u, hi); \
+                        const bool take = oh > hi || (oh == hi && ol > lo); lo = take ? ol : lo; hi = take ? oh : hi; }
+    GC_DPP_SCAN_STEPS(GC_STEP)
+#undef GC_STEP
+    return ((uint64_t)hi << 32) | lo;
+#endif
+}
+// Wave-wide shift by one lane away from lane 0: lane t receives the value of lane t - 1, lane 0 receives `fill` (wave_shr:1; turns an inclusive scan into an exclusive one)
+__device__ __forceinline__ uint32_t gc_wave_shr1(uint32_t v, uint32_t fill)
+{
+#ifdef HIPEMU
+    const uint32_t o = __shfl_up(v, 1);
+    return (__lane_id() & 63u) == 0u ? fill : o;
+#else
+    return gc_dpp_mov<0x138, 0xF>(fill, v);
+#endif
+}
+
 // Wave "publish / peek": every lane contributes one 32-bit value, afterwards any lane's value can be read with a
 // wave-uniform index.  On gfx950 this is a plain VGPR + v_readlane_b32 (result in an SGPR, so everything computed from it
 // stays on the scalar unit); under the emulator the values are copied out once per publish instead of once per peek.

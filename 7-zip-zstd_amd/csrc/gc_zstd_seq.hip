@@ -5,7 +5,7 @@
 // FSE_normalizeCount / FSE_writeNCount / FSE_buildCTable_wksp) and ZSTD_encodeSequences_body
 // (zstd_compress_sequences.c:291-383).
 //
-//   K3a codes   workgroup of 256 per block, parallel over sequences:
+//   K3a codes   workgroup of 256 per block, parallel over sequences, SEQ_R raw records per thread and round:
 //                 merge    chains of capped matches (same offset, litLength 0) collapse into one sequence
 //                 repcode  repeat-offset history as a scan: rep1 = previous offset, rep2 = the offset before the current run
 //                          of equal offsets.  Only codes whose meaning depends on (rep1, rep2) are emitted, so the decoder's
@@ -15,7 +15,7 @@
 //   K3c chains  ONE WAVE per (block, table) walks the table's FSE state backwards over all sequences: 64 segments at once, each lane
 //               finding its start state by running a few symbols ahead of its segment (FSE states forget their origin), checked and
 //               repaired against the predecessor's final state, so the result is exactly the serial walk
-//   K3d pack    workgroup of 256 per block: per-sequence bit counts -> prefix sums -> fields OR-ed into an LDS tile -> bytes stream out
+//   K3d pack    workgroup of 256 per block, SEQ_R sequences per thread and round: per-sequence bit counts -> prefix sums -> fields OR-ed into an LDS tile -> bytes stream out
 //
 // Why four: as one kernel (rounds 1-2) a block held 8 waves and 53 KB of LDS for the whole time while its serial middle (tables: three
 // lanes, chains: three waves; 70 % of the block's time) ran -- three blocks per CU, a machine mostly waiting.  Apart, the serial stages are
@@ -27,13 +27,18 @@
 #include "gc_device.h"
 #include "gc_fse.h"
 #include "gpucodec.h"      // gc_batch_item
+#include <type_traits>
 #ifdef HIPEMU
 #include <stdio.h>
 #include <stdlib.h>
 #endif
 
 #define SEQ_T GC_SEQ_T
-#define SEQ_TILE_WORDS ((SEQ_T * 80u) / 32u + 8u)
+#ifndef SEQ_R
+#define SEQ_R 4u             // K3a / K3d: sequences per thread and round (2 or 4; profiles/seq_rounds.md has both)
+#endif
+#define SEQ_N (SEQ_T * SEQ_R)                            // ... per workgroup and round
+#define SEQ_TILE_WORDS ((SEQ_N * 80u) / 32u + 8u)
 #define SEQ_CHAIN_TILE GC_SEQ_CHAIN_TILE   // sequences per state-chain tile
 #define SEQ_CHAIN_SEG  64u     // sequences per lane and tile
 #define SEQ_TC(u) ((u) + ((u) >> 6))                     // index of tile element u in tCode: row stride 65 bytes (a lane walks ITS segment, i.e.
@@ -55,8 +60,6 @@ __constant__ int16_t kLLDefNorm[36] = { 4,3,2,2,2,2,2,2,2,2,2,2,2,1,1,1,2,2,2,2,
 __constant__ int16_t kMLDefNorm[53] = { 1,4,3,2,2,2,2,2,2,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,-1,-1,-1,-1,-1,-1,-1 };
 __constant__ int16_t kOFDefNorm[29] = { 1,1,1,1,1,1,2,2,2,1,1,1,1,1,1,1,1,1,1,1,1,1,1,1,-1,-1,-1,-1,-1 };
 
-__device__ __forceinline__ uint32_t seq_ll_code(uint32_t ll) { return ll > 63u ? gc_hibit32(ll) + 19u : kLLCode[ll]; }
-__device__ __forceinline__ uint32_t seq_ml_code(uint32_t mlBase) { return mlBase > 127u ? gc_hibit32(mlBase) + 36u : kMLCode[mlBase]; }
 
 struct SeqTab {              // one FSE table in LDS (K3b builds it)
     uint16_t state[512];
@@ -70,31 +73,34 @@ struct SeqTab {              // one FSE table in LDS (K3b builds it)
     uint32_t tabMaxSym;      // last symbol described by norm[] (predefined: whole default table)
 };
 
-// block-wide exclusive sum scan (SEQ_T threads)
-__device__ __forceinline__ uint32_t seq_excl_scan(uint32_t v, uint32_t* sWave, uint32_t* total)
+// Block-wide scans of K3a / K3d (SEQ_T threads), one barrier each: the waves' totals go through sWave[par], and the caller flips `par` from call to call -- a wave
+// that writes its total of call k + 2 has passed the barrier of call k + 1, which no wave reaches before it has read the totals of call k.
+// exclusive sum
+__device__ __forceinline__ uint32_t seq_excl_scan(uint32_t v, uint32_t (*sWave)[SEQ_T / 64u], uint32_t& par, uint32_t* total)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = gc_wave_incl_sum(v);
-    if (lane == 63u) sWave[wave] = incl;
+    const uint32_t incl = gc_wave_incl_sum_dpp(v);
+    uint32_t* const W = sWave[par]; par ^= 1u;
+    if (lane == 63u) W[wave] = incl;
     __syncthreads();
     uint32_t before = 0, all = 0;
-    for (uint32_t w = 0; w < SEQ_T / 64u; w++) { uint32_t c = sWave[w]; if (w < wave) before += c; all += c; }
-    __syncthreads();
+    for (uint32_t w = 0; w < SEQ_T / 64u; w++) { uint32_t c = W[w]; if (w < wave) before += c; all += c; }
     *total = all;
     return before + incl - v;
 }
-// block-wide inclusive max scan
-__device__ __forceinline__ uint32_t seq_incl_maxscan(uint32_t v, uint32_t* sWave, uint32_t* total)
+// EXCLUSIVE max of 64-bit keys (0 in front of thread 0)
+__device__ __forceinline__ uint64_t seq_excl_maxscan64(uint64_t v, uint64_t (*sWave64)[SEQ_T / 64u], uint32_t& par, uint64_t* total)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = gc_wave_incl_max(v);
-    if (lane == 63u) sWave[wave] = incl;
+    const uint64_t incl = gc_wave_incl_max64_dpp(v);
+    uint64_t* const W = sWave64[par]; par ^= 1u;
+    if (lane == 63u) W[wave] = incl;
     __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (uint32_t w = 0; w < SEQ_T / 64u; w++) { uint32_t c = sWave[w]; if (w < wave) before = max(before, c); all = max(all, c); }
-    __syncthreads();
+    uint64_t before = 0, all = 0;
+    for (uint32_t w = 0; w < SEQ_T / 64u; w++) { const uint64_t c = W[w]; if (w < wave && c > before) before = c; if (c > all) all = c; }
     *total = all;
-    return max(before, incl);
+    const uint64_t left = ((uint64_t)gc_wave_shr1((uint32_t)(incl >> 32), 0u) << 32) | gc_wave_shr1((uint32_t)incl, 0u);      // the lane in front, 0 for lane 0
+    return before > left ? before : left;
 }
 
 __device__ __forceinline__ void seq_or_bits(uint32_t* buf, uint32_t bitoff, uint64_t v, uint32_t nbits)
@@ -166,27 +172,21 @@ __device__ inline void seq_build_table(SeqTab& T, int which, uint32_t nbSeq)
 #define SEQ_PHASE(i) do { if (prof && t == 0) { unsigned long long now_ = gc_clock(); atomicAdd(&prof[i], now_ - tprev); tprev = now_; } } while (0)
 
 // ------------------------------------------------------------------------------------------------ K3a codes
-// block-wide inclusive max scan of 64-bit keys (SEQ_T threads)
-__device__ __forceinline__ uint64_t seq_incl_maxscan64(uint64_t v, uint64_t* sWave64, uint64_t* total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t lo = __shfl_up((uint32_t)v, d), hi = __shfl_up((uint32_t)(v >> 32), d);
-        const uint64_t o = ((uint64_t)hi << 32) | lo;
-        if (lane >= (uint32_t)d && o > v) v = o;
-    }
-    if (lane == 63u) sWave64[wave] = v;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (uint32_t w = 0; w < SEQ_T / 64u; w++) { const uint64_t c = sWave64[w]; if (w < wave && c > before) before = c; if (c > all) all = c; }
-    __syncthreads();
-    *total = all;
-    return before > v ? before : v;
-}
+// A thread takes SEQ_R consecutive raw records per round (SEQ_N per workgroup); merged sequences collect in an LDS ring and are coded SEQ_R per thread from there, so
+// nothing this kernel computes is written to memory and read back (rounds 1-2 wrote the merged sequences out, then read them and their neighbours again).  A round
+// crosses four workgroup barriers (the scan of head counts, two around the ring, the scan of run keys) where one record per thread crossed eight.
+// One ring entry per merged sequence: ll | ml << 17 | off << 35 (17, 18 and 24 bits: a block has 2^17 bytes, a frame offsets below 2^24) -- a record that continues
+// a chain adds its length << 17.
+// The three code histograms are kept in SEQ_HIST_REPS copies, side by side per code.  LDS atomics of one wave instruction on one address are carried out one after
+// the other, and in text most sequences of a wave share a few codes: with one copy an instruction took as many passes as its most frequent code had lanes.
+#ifndef SEQ_HIST_REPS
+#define SEQ_HIST_REPS 8u
+#endif
+#define SEQ_RING (4u * SEQ_N)       // merged sequences the ring holds (> 2 * SEQ_N: up to SEQ_N wait for their batch to fill while a round adds up to SEQ_N)
+#define SEQ_ENT(ll, ml, off) ((uint64_t)(ll) | ((uint64_t)(ml) << 17) | ((uint64_t)(off) << 35))
+#define SEQ_ENT_OFF(e) ((uint32_t)((e) >> 35))
+struct __attribute__((aligned(16))) SeqP2 { uint64_t a, b; };      // two packed sequences: one global_store_dwordx4
 
-// The raw records are taken SEQ_T at a time; merged sequences collect in an LDS ring and are coded SEQ_T at a time from there, so nothing this
-// kernel computes is written to memory and read back (rounds 1-2 wrote the merged sequences out, then read them and their neighbours again).
-#define SEQ_RING 1024u       // merged sequences the ring holds (>= 2 * SEQ_T + 1)
 extern "C" __global__ void __launch_bounds__(SEQ_T)
 gc_zstd_seq_codes_kernel(const GcSeqRaw* __restrict__ seqRaw, const GcBlockMeta* __restrict__ meta,
                    uint64_t* __restrict__ seqPacked,      // out: ll | mlBase << 17 | offBase << 35 per merged sequence
@@ -196,11 +196,11 @@ gc_zstd_seq_codes_kernel(const GcSeqRaw* __restrict__ seqRaw, const GcBlockMeta*
                    uint32_t frameBlocks,                  // blocks per zstd frame: repeat offsets carry over inside a frame
                    unsigned long long* __restrict__ prof /* optional per-phase cycle sums */)
 {
-    __shared__ uint32_t sCount[3][64];
-    __shared__ uint32_t sWave[SEQ_T / 64u];
-    __shared__ uint64_t sWave64[SEQ_T / 64u];
-    __shared__ uint64_t sPair[SEQ_T];
-    __shared__ uint32_t rLL[SEQ_RING], rML[SEQ_RING], rOFF[SEQ_RING];
+    __shared__ uint32_t sCount[3][64][SEQ_HIST_REPS];   // a lane counts in copy lane % SEQ_HIST_REPS
+    __shared__ uint32_t sWave[2][SEQ_T / 64u];
+    __shared__ uint64_t sWave64[2][SEQ_T / 64u];
+    __shared__ uint64_t sRing[SEQ_RING];
+    __shared__ uint8_t sLLCode[64], sMLCode[128];         // kLLCode / kMLCode, staged: a per-lane read of a __constant__ table is a global load
     const uint32_t t = threadIdx.x, b = blockIdx.x;
     const uint32_t nRaw = meta[b].nSeqRaw;
     const GcSeqRaw* R = seqRaw + (uint64_t)b * GC_MAX_SEQ_PER_BLOCK;
@@ -210,7 +210,10 @@ gc_zstd_seq_codes_kernel(const GcSeqRaw* __restrict__ seqRaw, const GcBlockMeta*
     uint8_t* cML = cOF + GC_MAX_SEQ_PER_BLOCK;
     (void)seqOff;
     if (nRaw == 0) { if (t == 0) { seqSec[(uint64_t)b * GC_SEQSEC_STRIDE] = 0; info[b].seqSecSize = 1; info[b].nSeq = 0; } return; }
-    for (uint32_t i = t; i < 3u * 64u; i += SEQ_T) sCount[i >> 6][i & 63u] = 0;
+    for (uint32_t i = t; i < 3u * 64u * SEQ_HIST_REPS; i += SEQ_T) (&sCount[0][0][0])[i] = 0;
+    const uint32_t hrep = t & (SEQ_HIST_REPS - 1u);
+    if (t < 64u) sLLCode[t] = kLLCode[t];
+    if (t < 128u) sMLCode[t] = kMLCode[t];
     unsigned long long tprev = prof ? gc_clock() : 0ull;
 
     // virtual history of the repeat offsets: index -1 -> offset 1, -2 -> 4 (start state {1,4,8}, zstd_internal.h:65) in the first block of a
@@ -221,76 +224,137 @@ gc_zstd_seq_codes_kernel(const GcSeqRaw* __restrict__ seqRaw, const GcBlockMeta*
     const bool firstInFrame = (b % frameBlocks) == 0u;
     const uint32_t virt1 = firstInFrame ? 1u : 0u, virt2 = firstInFrame ? 4u : 0u;
     uint32_t nMerged = 0, nCoded = 0;        // merged sequences in the ring so far / coded so far (uniform)
+    uint32_t par = 0, par64 = 0;             // which half of sWave / sWave64 the next scan takes
     uint32_t carryOff = virt1;               // offset of the last coded sequence
     uint64_t carryPair = (1ull << 32) | virt2;   // (start index + 2 of the run of equal offsets that holds the last coded sequence, offset in front of that run)
 
-    // S2 on the SEQ_T sequences from nCoded on (or the last few): repeat offsets as scans, codes, histograms
-    auto code_batch = [&](uint32_t count) {
-        const uint32_t j = nCoded + t;
-        const bool on = t < count;
-        uint32_t off = 0, prevOff = carryOff, ll = 0, ml = 0;
-        if (on) {
-            off = rOFF[j & (SEQ_RING - 1u)]; ll = rLL[j & (SEQ_RING - 1u)]; ml = rML[j & (SEQ_RING - 1u)];
-            if (t) prevOff = rOFF[(j - 1u) & (SEQ_RING - 1u)];
+    // S2 on the SEQ_N sequences from nCoded on (or the last few), SEQ_R consecutive ones per thread: repeat offsets as scans, codes, histograms.
+    // (nCoded is a multiple of SEQ_N in every call: only the block's last batch is short.  `whole`: count == SEQ_N, known where the call is written -- every thread
+    // has SEQ_R sequences and the per-sequence conditions fold away.)
+    auto code_batch = [&](uint32_t count, auto whole) {
+        const uint32_t j0 = nCoded + t * SEQ_R;
+        const uint32_t mine = decltype(whole)::value ? SEQ_R : (t * SEQ_R < count ? min(SEQ_R, count - t * SEQ_R) : 0u);
+        uint64_t e[SEQ_R], keyIn[SEQ_R]; uint32_t prevOff[SEQ_R];
+        uint32_t pOff = carryOff;
+        if (mine && t) pOff = SEQ_ENT_OFF(sRing[(j0 - 1u) & (SEQ_RING - 1u)]);
+        // a run of equal offsets starts at j: key = (j + 2, the offset in front of the run); the scan hands every j the key of its run.  Keys grow with j, so the
+        // maximum over a thread's sequences is the last key among them: a thread scans its own, the workgroup the threads' last keys.
+        uint64_t run = 0;
+#pragma unroll
+        for (uint32_t r = 0; r < SEQ_R; r++) {
+            e[r] = 0; prevOff[r] = pOff; keyIn[r] = run;
+            if (r < mine) {
+                e[r] = sRing[(j0 + r) & (SEQ_RING - 1u)];
+                const uint32_t off = SEQ_ENT_OFF(e[r]);
+                if (off != pOff) run = (((uint64_t)(j0 + r + 2u)) << 32) | pOff;
+                pOff = off;
+            }
         }
-        // a run of equal offsets starts at j: key = (j + 2, the offset in front of the run); the scan hands every j the key of its run
-        const uint64_t key = (on && off != prevOff) ? (((uint64_t)(j + 2u)) << 32) | prevOff : 0ull;
         uint64_t tot;
-        uint64_t pair = seq_incl_maxscan64(key, sWave64, &tot);
-        if (carryPair > pair) pair = carryPair;
-        sPair[t] = pair;
-        __syncthreads();
-        const uint64_t pairPrev = t ? sPair[t - 1u] : carryPair;                   // ... of the run that holds j - 1
-        if (on) {
-            const uint32_t rep1 = prevOff, rep2 = (uint32_t)pairPrev;
-            uint32_t offBase;
-            if (ll != 0u) offBase = (off == rep1) ? 1u : ((off == rep2) ? 2u : off + 3u);
-            else offBase = (off == rep2) ? 1u : ((rep1 > 1u && off == rep1 - 1u) ? 3u : off + 3u);
-            const uint32_t mlBase = ml - 3u;
-            const uint32_t llc = seq_ll_code(ll), mlc = seq_ml_code(mlBase), ofc = gc_hibit32(offBase);
-            cLL[j] = (uint8_t)llc; cOF[j] = (uint8_t)ofc; cML[j] = (uint8_t)mlc;
-            atomicAdd(&sCount[0][llc], 1u); atomicAdd(&sCount[1][ofc], 1u); atomicAdd(&sCount[2][mlc], 1u);
-            P[j] = (uint64_t)ll | ((uint64_t)mlBase << 17) | ((uint64_t)offBase << 35);   // ll, mlBase, offBase
+        uint64_t front = seq_excl_maxscan64(run, sWave64, par64, &tot);       // ... of the run that holds the sequence in front of this thread's first
+        if (carryPair > front) front = carryPair;
+        uint32_t packLL = 0, packOF = 0, packML = 0; uint64_t pk[SEQ_R];
+#pragma unroll
+        for (uint32_t r = 0; r < SEQ_R; r++) {
+            pk[r] = 0;
+            if (r < mine) {
+                const uint32_t j = j0 + r;
+                const uint64_t pairPrev = keyIn[r] > front ? keyIn[r] : front;      // ... of the run that holds j - 1
+                const uint32_t ll = (uint32_t)e[r] & 0x1FFFFu, ml = (uint32_t)(e[r] >> 17) & 0x3FFFFu, off = SEQ_ENT_OFF(e[r]);
+                const uint32_t rep1 = prevOff[r], rep2 = (uint32_t)pairPrev;
+                uint32_t offBase;
+                if (ll != 0u) offBase = (off == rep1) ? 1u : ((off == rep2) ? 2u : off + 3u);
+                else offBase = (off == rep2) ? 1u : ((rep1 > 1u && off == rep1 - 1u) ? 3u : off + 3u);
+                const uint32_t mlBase = ml - 3u;
+                const uint32_t llc = ll > 63u ? gc_hibit32(ll) + 19u : sLLCode[ll], mlc = mlBase > 127u ? gc_hibit32(mlBase) + 36u : sMLCode[mlBase], ofc = gc_hibit32(offBase);
+                packLL |= llc << (8u * r); packOF |= ofc << (8u * r); packML |= mlc << (8u * r);
+                atomicAdd(&sCount[0][llc][hrep], 1u); atomicAdd(&sCount[1][ofc][hrep], 1u); atomicAdd(&sCount[2][mlc][hrep], 1u);
+                pk[r] = (uint64_t)ll | ((uint64_t)mlBase << 17) | ((uint64_t)offBase << 35);   // ll, mlBase, offBase
 #ifdef HIPEMU
-            if (getenv("GC_TRACE")) fprintf(stderr, "E %u ofv=%u ml=%u ll=%u off=%u rep1=%u rep2=%u\n", j, offBase, ml, ll, off, rep1, rep2);
+                if (getenv("GC_TRACE")) fprintf(stderr, "E %u ofv=%u ml=%u ll=%u off=%u rep1=%u rep2=%u\n", j, offBase, ml, ll, off, rep1, rep2);
 #endif
+            }
+        }
+        if (mine == SEQ_R) {                 // whole: SEQ_R code bytes per table in one store (the tables' bases are only 2-byte aligned), the packed words 16 bytes at a time
+            __builtin_memcpy(cLL + j0, &packLL, SEQ_R); __builtin_memcpy(cOF + j0, &packOF, SEQ_R); __builtin_memcpy(cML + j0, &packML, SEQ_R);
+#pragma unroll
+            for (uint32_t r = 0; r < SEQ_R; r += 2u) { SeqP2 v; v.a = pk[r]; v.b = pk[r + 1u]; *(SeqP2*)(P + j0 + r) = v; }
+        } else {
+#pragma unroll
+            for (uint32_t r = 0; r < SEQ_R; r++)
+                if (r < mine) { cLL[j0 + r] = (uint8_t)(packLL >> (8u * r)); cOF[j0 + r] = (uint8_t)(packOF >> (8u * r)); cML[j0 + r] = (uint8_t)(packML >> (8u * r)); P[j0 + r] = pk[r]; }
         }
         if (tot > carryPair) carryPair = tot;
-        carryOff = rOFF[(nCoded + count - 1u) & (SEQ_RING - 1u)];
+        carryOff = SEQ_ENT_OFF(sRing[(nCoded + count - 1u) & (SEQ_RING - 1u)]);
         nCoded += count;
-        __syncthreads();
     };
 
-    GcSeqRaw rNext, qNext;                   // this thread's record of the next round and the record in front of it (requested a round ahead)
-    rNext.litRank = rNext.offml = qNext.litRank = qNext.offml = 0;
-    if (t < nRaw) { rNext = R[t]; if (t) qNext = R[t - 1u]; }
-    for (uint32_t tb = 0; tb < nRaw; tb += SEQ_T) {
-        // ---- S1: merge chains of capped matches.  Head = first record of a run with equal offset and litLength 0; the records behind it
-        //      add their lengths to it (a chain may run on into the next SEQ_T records: the ring's last sequence stays open until then)
-        const uint32_t i = tb + t;
-        const GcSeqRaw r = rNext, q = qNext;
-        if (i + SEQ_T < nRaw) { rNext = R[i + SEQ_T]; qNext = R[i + SEQ_T - 1u]; }
-        uint32_t head = 0, ll = 0, off = 0, ml = 0;
-        if (i < nRaw) {
-            uint32_t prevRank = 0, prevOff = 0;
-            if (i) { prevRank = q.litRank; prevOff = q.offml >> 8; }
-            ll = r.litRank - prevRank; off = r.offml >> 8; ml = r.offml & 0xFFu;
-            head = (i == 0u || ll != 0u || off != prevOff) ? 1u : 0u;
+    // this thread's records of a round and the record in front of them (requested a round ahead)
+    auto load_records = [&](uint32_t i0, GcSeqRaw (&r)[SEQ_R], GcSeqRaw& q) {
+#pragma unroll
+        for (uint32_t k = 0; k < SEQ_R; k++) r[k].litRank = r[k].offml = 0;
+        q.litRank = q.offml = 0;
+        if (i0 >= nRaw) return;
+        if (i0 + SEQ_R <= nRaw) {           // (16 bytes at a time: a block's records start 16-byte aligned, GC_MAX_SEQ_PER_BLOCK is even)
+#pragma unroll
+            for (uint32_t k = 0; k < SEQ_R; k += 2u) {
+                const GcU4 v = *(const GcU4*)(R + i0 + k);
+                r[k].litRank = v.x; r[k].offml = v.y; r[k + 1u].litRank = v.z; r[k + 1u].offml = v.w;
+            }
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < SEQ_R; k++) if (i0 + k < nRaw) r[k] = R[i0 + k];
         }
+        if (i0) q = R[i0 - 1u];
+    };
+    GcSeqRaw rNext[SEQ_R], qNext;
+    load_records(t * SEQ_R, rNext, qNext);
+    for (uint32_t tb = 0; tb < nRaw; tb += SEQ_N) {
+        // ---- S1: merge chains of capped matches.  Head = first record of a run with equal offset and litLength 0; the records behind it
+        //      add their lengths to it (a chain may run on into the next thread's records or the next round's: the ring's last sequence stays open until then)
+        const uint32_t i0 = tb + t * SEQ_R;
+        const bool wholeRound = tb + SEQ_N <= nRaw;       // (uniform)
+        uint32_t ll[SEQ_R], off[SEQ_R], ml[SEQ_R]; bool valid[SEQ_R], head[SEQ_R];
+        uint32_t nHead = 0;
+        {
+            uint32_t prevRank = qNext.litRank, prevOff = qNext.offml >> 8;      // (both 0 in front of record 0, which is a head whatever they are)
+#pragma unroll
+            for (uint32_t k = 0; k < SEQ_R; k++) {
+                const uint32_t i = i0 + k;
+                valid[k] = wholeRound || i < nRaw;
+                ll[k] = rNext[k].litRank - prevRank; off[k] = rNext[k].offml >> 8; ml[k] = rNext[k].offml & 0xFFu;
+                head[k] = valid[k] && (i == 0u || ll[k] != 0u || off[k] != prevOff);
+                nHead += head[k] ? 1u : 0u;
+                prevRank = rNext[k].litRank; prevOff = off[k];
+            }
+        }
+        load_records(i0 + SEQ_N, rNext, qNext);
         uint32_t tot;
-        const uint32_t before = seq_excl_scan(head, sWave, &tot);
-        const uint32_t slot = (nMerged + before + head - 1u) & (SEQ_RING - 1u);      // (a record that is no head: the sequence of the head in front of it)
-        if (head) { rLL[slot] = ll; rML[slot] = ml; rOFF[slot] = off; }
+        const uint32_t before = seq_excl_scan(nHead, sWave, par, &tot);
+        // the thread folds its own records: a sequence goes into the ring when the next head closes it (or the thread's records end: it may still grow); the
+        // records in front of the thread's first head belong to the sequence of the head in front of them, in another thread's hands or an earlier round's
+        uint32_t slot = nMerged + before, leadMl = 0; bool open = false; uint64_t cur = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < SEQ_R; k++) {
+            if (head[k]) { if (open) { sRing[slot & (SEQ_RING - 1u)] = cur; slot++; } cur = SEQ_ENT(ll[k], ml[k], off[k]); open = true; }
+            else if (valid[k]) { if (open) cur += (uint64_t)ml[k] << 17; else leadMl += ml[k]; }
+        }
+        if (open) sRing[slot & (SEQ_RING - 1u)] = cur;
         __syncthreads();
-        if (i < nRaw && !head) atomicAdd(&rML[slot], ml);
+        if (leadMl) atomicAdd((unsigned long long*)&sRing[(nMerged + before - 1u) & (SEQ_RING - 1u)], (unsigned long long)leadMl << 17);
         nMerged += tot;
         __syncthreads();
-        // ---- S2 whenever SEQ_T sequences are complete (the last one in the ring may still grow)
-        while (nMerged - nCoded > SEQ_T) code_batch(SEQ_T);
+        // ---- S2 whenever SEQ_N sequences are complete (the last one in the ring may still grow)
+        while (nMerged - nCoded > SEQ_N) code_batch(SEQ_N, std::true_type());
     }
     SEQ_PHASE(0);         // merge (and the batches coded on the way)
-    while (nCoded < nMerged) code_batch(nMerged - nCoded < SEQ_T ? nMerged - nCoded : SEQ_T);
-    for (uint32_t i = t; i < 3u * 64u; i += SEQ_T) hist[b].count[i >> 6][i & 63u] = sCount[i >> 6][i & 63u];
+    while (nCoded < nMerged) code_batch(nMerged - nCoded < SEQ_N ? nMerged - nCoded : SEQ_N, std::false_type());
+    __syncthreads();
+    for (uint32_t i = t; i < 3u * 64u; i += SEQ_T) {
+        uint32_t n = 0;
+        for (uint32_t k = 0; k < SEQ_HIST_REPS; k++) n += sCount[i >> 6][i & 63u][k];
+        hist[b].count[i >> 6][i & 63u] = n;
+    }
     if (t == 0) info[b].nSeq = nMerged;
     SEQ_PHASE(1);         // repcodes + codes + histograms
 }
@@ -463,16 +527,28 @@ gc_zstd_seq_chain_kernel(const uint8_t* __restrict__ codes, const GcSectionInfo*
 }
 
 // ------------------------------------------------------------------------------------------------ K3d pack
-struct SeqPackLds { uint32_t wave[SEQ_T / 64u]; uint32_t tile[SEQ_TILE_WORDS]; uint32_t mode[3], log[3], fin[3], desc[3]; };      // the calling kernel's LDS
+struct SeqPackLds { uint32_t wave[2][SEQ_T / 64u]; uint32_t tile[SEQ_TILE_WORDS]; uint32_t mode[3], log[3], fin[3], desc[3]; uint8_t llBits[40], mlBits[56]; };      // the calling kernel's LDS
+
+// One round's input of a thread: SEQ_R sequences, requested a round ahead.  Wave w takes the elements tb + 64 * (SEQ_R * w + s) + lane, s < SEQ_R, of a round (element u is
+// sequence nSeq - 1 - u): for every s the wave reads 64 neighbouring packed words and code bytes, and its SEQ_R states of one table lie side by side in SEQ_ST_IDX's order,
+// which groups four 64-element segments per 512 bytes -- one load per table and lane, whole lines per wave.
+#if SEQ_R == 4u
+typedef uint64_t SeqStWord;
+#elif SEQ_R == 2u
+typedef uint32_t SeqStWord;
+#else
+#error "SEQ_R is 2 or 4: the states of SEQ_R segments are one aligned load"
+#endif
+struct SeqPackIn { uint64_t pk[SEQ_R]; uint32_t codes[SEQ_R]; SeqStWord st[3]; };     // codes: LL | OF << 8 | ML << 16; st: LL, OF, ML
 
 // block b of the workspace, whose content is blockLen bytes long (a section that does not stay below that is given up: the block is stored raw)
 __device__ __forceinline__ void seq_pack_block(const uint64_t* __restrict__ seqPacked, const uint8_t* __restrict__ codes, const uint16_t* __restrict__ states,
                                                const GcSeqTabG* __restrict__ tabs, uint8_t* __restrict__ seqSec, GcSectionInfo* __restrict__ info,
                                                const uint32_t b, const uint32_t blockLen, unsigned long long* __restrict__ prof, SeqPackLds& L)
 {
-    uint32_t* const sWave = L.wave; uint32_t* const sTile = L.tile;
+    uint32_t* const sTile = L.tile;
     uint32_t* const sMode = L.mode; uint32_t* const sLog = L.log; uint32_t* const sFinal = L.fin; uint32_t* const sDesc = L.desc;
-    const uint32_t t = threadIdx.x;
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
     const uint32_t nSeq = info[b].nSeq;
     if (nSeq == 0u) return;                                   // (the codes kernel has written the one-byte section)
     unsigned long long tprev = prof ? gc_clock() : 0ull;
@@ -486,6 +562,8 @@ __device__ __forceinline__ void seq_pack_block(const uint64_t* __restrict__ seqP
     const GcSeqTabG* G = tabs + (uint64_t)b * 3u;
     uint8_t* out = seqSec + (uint64_t)b * GC_SEQSEC_STRIDE;
     if (t < 3u) { sMode[t] = G[t].mode; sLog[t] = G[t].tableLog; sFinal[t] = G[t].finalState; sDesc[t] = G[t].descSize; }
+    if (t < 36u) L.llBits[t] = kLLBits[t];                    // (staged: a per-lane read of a __constant__ table is a global load)
+    if (t >= 64u && t < 64u + 53u) L.mlBits[t - 64u] = kMLBits[t - 64u];
     __syncthreads();
 
     // ---- section header (zstd_compress.c:2939-2953 nbSeq; modes byte; table descriptions LL, OF, ML)
@@ -504,38 +582,73 @@ __device__ __forceinline__ void seq_pack_block(const uint64_t* __restrict__ seqP
     }
     const bool rleLL = sMode[0] == 1u, rleOF = sMode[1] == 1u, rleML = sMode[2] == 1u;
 
+    const uint32_t uWave = 64u * SEQ_R * wave + lane;         // this thread's elements of a round: tb + uWave + 64 * s
+    const uint32_t stWave = ((64u * SEQ_R * wave) & ~255u) + 4u * lane + ((SEQ_R * wave) & 3u);      // SEQ_ST_IDX of the first of them (behind tb)
+    auto fetch = [&](uint32_t tb, SeqPackIn& in) {
+#pragma unroll
+        for (uint32_t s = 0; s < SEQ_R; s++) {
+            const uint32_t u = tb + uWave + 64u * s;
+            in.pk[s] = 0; in.codes[s] = 0;
+            if (u < nSeq) { const uint32_t j = nSeq - 1u - u; in.pk[s] = P[j]; in.codes[s] = (uint32_t)cLL[j] | ((uint32_t)cOF[j] << 8) | ((uint32_t)cML[j] << 16); }
+        }
+        in.st[0] = in.st[1] = in.st[2] = 0;
+        if (tb + uWave < nSeq) {           // (a table in RLE mode has no states: the chain kernel wrote none)
+            if (!rleLL) in.st[0] = *(const SeqStWord*)(stLL + tb + stWave);
+            if (!rleOF) in.st[1] = *(const SeqStWord*)(stOF + tb + stWave);
+            if (!rleML) in.st[2] = *(const SeqStWord*)(stML + tb + stWave);
+        }
+    };
+
     // ---- pack the bitstream, last sequence first
     const uint32_t limit = min(blockLen, (uint32_t)GC_SEQSEC_STRIDE - 64u);
     uint8_t* so = out + hdrLen;
-    uint32_t carryBits = 0, carryVal = 0, outBytes = 0; bool overflow = false;
-    for (uint32_t tb = 0; tb < nSeq && !overflow; tb += SEQ_T) {
-        for (uint32_t i = t; i < SEQ_TILE_WORDS; i += SEQ_T) sTile[i] = 0;
-        __syncthreads();
-        const uint32_t u = tb + t;
-        uint64_t a = 0, c = 0; uint32_t na = 0, nc = 0;
-        if (u < nSeq) {
-            const uint32_t j = nSeq - 1u - u;
-            const uint64_t pk = P[j];
-            const uint32_t ll = (uint32_t)(pk & 0x1FFFFu), mlBase = (uint32_t)((pk >> 17) & 0x3FFFFu), offBase = (uint32_t)(pk >> 35);
-            const uint32_t llc = cLL[j], mlc = cML[j], ofc = cOF[j];
-            if (u != 0u) {
-                const uint32_t si = SEQ_ST_IDX(u);
-                const uint32_t so_ = rleOF ? 0u : stOF[si], sm = rleML ? 0u : stML[si], sl = rleLL ? 0u : stLL[si];
-                a |= (uint64_t)(so_ & ((1u << (so_ >> 10)) - 1u)) << na; na += so_ >> 10;     // low nbBits of the state (stored whole)
-                a |= (uint64_t)(sm & ((1u << (sm >> 10)) - 1u)) << na; na += sm >> 10;
-                a |= (uint64_t)(sl & ((1u << (sl >> 10)) - 1u)) << na; na += sl >> 10;
+    uint32_t carryBits = 0, carryVal = 0, outBytes = 0, par = 0; bool overflow = false;
+    SeqPackIn nx;
+    fetch(0u, nx);
+    for (uint32_t tb = 0; tb < nSeq && !overflow; tb += SEQ_N) {
+        const uint32_t tileWords = (min(SEQ_N, nSeq - tb) * 80u) / 32u + 8u;       // what this round's sequences can fill
+        for (uint32_t i = t; i < tileWords; i += SEQ_T) sTile[i] = 0;
+        const SeqPackIn in = nx;
+        if (tb + SEQ_N < nSeq) fetch(tb + SEQ_N, nx);
+        uint64_t a[SEQ_R], c[SEQ_R]; uint32_t na[SEQ_R], nc[SEQ_R], incl[SEQ_R];
+        uint32_t waveBits = 0;
+#pragma unroll
+        for (uint32_t s = 0; s < SEQ_R; s++) {
+            const uint32_t u = tb + uWave + 64u * s;
+            a[s] = 0; c[s] = 0; na[s] = 0; nc[s] = 0;
+            if (u < nSeq) {
+                const uint64_t pk = in.pk[s];
+                const uint32_t ll = (uint32_t)(pk & 0x1FFFFu), mlBase = (uint32_t)((pk >> 17) & 0x3FFFFu), offBase = (uint32_t)(pk >> 35);
+                const uint32_t llc = in.codes[s] & 0xFFu, ofc = (in.codes[s] >> 8) & 0xFFu, mlc = in.codes[s] >> 16;
+                if (u != 0u) {
+                    const uint32_t so_ = (uint32_t)(in.st[1] >> (16u * s)) & 0xFFFFu, sm = (uint32_t)(in.st[2] >> (16u * s)) & 0xFFFFu, sl = (uint32_t)(in.st[0] >> (16u * s)) & 0xFFFFu;
+                    a[s] |= (uint64_t)(so_ & ((1u << (so_ >> 10)) - 1u)) << na[s]; na[s] += so_ >> 10;     // low nbBits of the state (stored whole)
+                    a[s] |= (uint64_t)(sm & ((1u << (sm >> 10)) - 1u)) << na[s]; na[s] += sm >> 10;
+                    a[s] |= (uint64_t)(sl & ((1u << (sl >> 10)) - 1u)) << na[s]; na[s] += sl >> 10;
+                }
+                { uint32_t nb = L.llBits[llc]; a[s] |= (uint64_t)(ll & ((1u << nb) - 1u)) << na[s]; na[s] += nb; }
+                { uint32_t nb = L.mlBits[mlc]; c[s] |= (uint64_t)(mlBase & ((1u << nb) - 1u)); nc[s] += nb; }
+                { c[s] |= (uint64_t)(offBase & ((1u << ofc) - 1u)) << nc[s]; nc[s] += ofc; }
             }
-            { uint32_t nb = kLLBits[llc]; a |= (uint64_t)(ll & ((1u << nb) - 1u)) << na; na += nb; }
-            { uint32_t nb = kMLBits[mlc]; c |= (uint64_t)(mlBase & ((1u << nb) - 1u)); nc += nb; }
-            { c |= (uint64_t)(offBase & ((1u << ofc) - 1u)) << nc; nc += ofc; }
+            // bit offsets: the wave's elements are ordered s first, lane second -- a wave scan per s, the totals of the s in front added
+            incl[s] = gc_wave_incl_sum_dpp(na[s] + nc[s]) + waveBits;
+            waveBits = gc_readlane(incl[s], 63u);
         }
-        uint32_t tileBits;
-        const uint32_t off = seq_excl_scan(na + nc, sWave, &tileBits) + carryBits;
+        // ... and one barrier for the waves' totals (it also stands between the zeroing of the tile and the fields OR-ed into it)
+        uint32_t* const W = L.wave[par]; par ^= 1u;
+        if (lane == 63u) W[wave] = waveBits;
+        __syncthreads();
+        uint32_t before = carryBits, tileBits = 0;
+        for (uint32_t w = 0; w < SEQ_T / 64u; w++) { const uint32_t v = W[w]; if (w < wave) before += v; tileBits += v; }
         if (t == 0 && carryBits) atomicOr(&sTile[0], carryVal);
-        seq_or_bits(sTile, off, a, na);
-        seq_or_bits(sTile, off + na, c, nc);
+#pragma unroll
+        for (uint32_t s = 0; s < SEQ_R; s++) {
+            const uint32_t off = before + incl[s] - (na[s] + nc[s]);
+            seq_or_bits(sTile, off, a[s], na[s]);
+            seq_or_bits(sTile, off + na[s], c[s], nc[s]);
+        }
         uint32_t endBits = carryBits + tileBits;
-        const bool lastTile = tb + SEQ_T >= nSeq;
+        const bool lastTile = tb + SEQ_N >= nSeq;
         if (lastTile) {
             if (t == 0) {      // final states ML, OF, LL then the closing bit (zstd_compress_sequences.c:372-376)
                 uint32_t e = endBits;
@@ -550,7 +663,15 @@ __device__ __forceinline__ void seq_pack_block(const uint64_t* __restrict__ seqP
         const uint32_t flush = lastTile ? (endBits + 7u) >> 3 : endBits >> 3;
         if (hdrLen + outBytes + flush > limit) overflow = true;
         else {
-            for (uint32_t i = t; i < flush; i += SEQ_T) so[outBytes + i] = (uint8_t)(sTile[i >> 2] >> ((i & 3u) * 8u));
+            // the round's bytes leave as aligned dwords, single bytes only in front of the first and behind the last of them
+            uint8_t* const dst = so + outBytes;
+            const uint32_t lead = min(flush, (uint32_t)(0u - (uint32_t)(uintptr_t)dst) & 3u), nWords = (flush - lead) >> 2, tail = lead + 4u * nWords;
+            if (t < lead) dst[t] = (uint8_t)(sTile[0] >> (t * 8u));
+            for (uint32_t i = t; i < nWords; i += SEQ_T) {
+                const uint32_t w = lead ? (uint32_t)((((uint64_t)sTile[i + 1u] << 32) | sTile[i]) >> (lead * 8u)) : sTile[i];
+                *(uint32_t*)(dst + lead + 4u * i) = w;
+            }
+            if (t >= SEQ_T - 4u && tail + (t - (SEQ_T - 4u)) < flush) { const uint32_t i = tail + (t - (SEQ_T - 4u)); dst[i] = (uint8_t)(sTile[i >> 2] >> ((i & 3u) * 8u)); }
             carryBits = endBits & 7u;
             carryVal = lastTile ? 0u : ((sTile[flush >> 2] >> ((flush & 3u) * 8u)) & 0xFFu);
             outBytes += flush;
@@ -581,4 +702,15 @@ gc_zstd_seq_pack_batch_kernel(const uint64_t* __restrict__ seqPacked, const uint
 {
     __shared__ SeqPackLds L;
     seq_pack_block(seqPacked, codes, states, tabs, seqSec, info, blockIdx.x, items[blockIdx.x].src_size, nullptr, L);
+}
+
+// ------------------------------------------------------------------------------------------------ the wave scans of gc_device.h, for the tests
+// (gc_api.hip gc_test_wave_scans, test builds only) one wave per 64 values
+extern "C" __global__ void __launch_bounds__(64)
+gc_wave_scan_test_kernel(const uint32_t* __restrict__ v, const uint64_t* __restrict__ keys, uint32_t* __restrict__ sum, uint32_t* __restrict__ mx, uint64_t* __restrict__ mx64)
+{
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    sum[i] = gc_wave_incl_sum_dpp(v[i]);
+    mx[i] = gc_wave_incl_max_dpp(v[i]);
+    mx64[i] = gc_wave_incl_max64_dpp(keys[i]);
 }
