@@ -904,6 +904,25 @@ class ZstdEncoder(_ZstdDictionary, _EncoderBase):
         self._check(fn(self._ctx, vv.ctypes.data, kk.ctypes.data, m, s.ctypes.data, mx.ctypes.data, mx64.ctypes.data), "gc_test_wave_scans")
         return s[:n], mx[:n], mx64[:n]
 
+    def mf_lists(self, data, fast, mode, frame_blocks):
+        """TEST BUILDS ONLY: W1..W3 of the windowed finder (gc_api.hip gc_test_mf_lists) on the bytes `data`: one geometry (fast: 256 partitions, 8 KiB tiles; else
+        1024 partitions, 16 KiB tiles), one key mode (0 base, 1 far, 2 short, 4 far2), frames of frame_blocks blocks -> (offsets [frame][tile 0 .. tiles per
+        frame][partition] uint32, entries [frame][frame bytes] uint64; what lies outside the runs is 0xFF bytes)."""
+        import numpy as np
+        fn = getattr(self._lib, "gc_test_mf_lists", None)
+        if fn is None:
+            raise GpuCodecError("gc_test_mf_lists: this library is not a test build")
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+        fn.restype = C.c_int
+        x = np.ascontiguousarray(data, dtype=np.uint8).ravel()
+        blk, tile, parts = 128 << 10, (8 << 10) if fast else (16 << 10), 256 if fast else 1024
+        frames = -(-(-(-x.size // blk)) // frame_blocks)
+        tpf = frame_blocks * (blk // tile)
+        offs = np.zeros((frames, tpf + 1, parts), np.uint32)
+        ent = np.zeros((frames, frame_blocks * blk), np.uint64)
+        self._check(fn(self._ctx, x.ctypes.data, x.size, int(bool(fast)), int(mode), int(frame_blocks), offs.ctypes.data, ent.ctypes.data), "gc_test_mf_lists")
+        return offs, ent
+
     # ---- batches: many independent inputs of at most BATCH_ITEM_MAX bytes, one frame each, in one launch set (include/gpucodec.h "ZSTD, batched")
     BATCH_ITEM_MAX = 128 << 10
     BATCH_KERNELS = ("lz", "entropy", "frame", "total")

@@ -1010,6 +1010,46 @@ extern "C" int gc_test_wave_scans(gc_ctx* c, const uint32_t* v, const uint64_t* 
     if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "gc_test_wave_scans failed: %s", hipGetErrorString(e)); return GC_ERR_HIP; }
     return GC_OK;
 }
+
+// Test entry (the test builds only): W1..W3 of ONE key mode (0 base, 1 far, 2 short, 4 far2: gc_lz_window.hip MF_*) and one geometry over frames of frameBlocks blocks
+// (2..64, no overlap), so that a test sees the lists themselves -- which of W1 and W3 disagrees with a model, where a stream hash only says that something does.
+// HOST memory throughout: src[n] is copied to the device; offs receives the offsets table after W2 (gc_mf_geom(n, frameBlocks, fast).cntWords words: [frame][tile 0 ..
+// tilesPerFrame][partition]), ent the entry array after W3 (nFrames * frameBlocks * 128 Ki entries; what lies outside the runs is 0xFF bytes).
+extern "C" int gc_test_mf_lists(gc_ctx* c, const uint8_t* src, size_t n, int fast, int mode, uint32_t frameBlocks, uint32_t* offs, uint64_t* ent)
+{
+    if (!c || !src || !n || !offs || !ent || frameBlocks < 2u || frameBlocks > GC_MF_MAX_FRAME_BLOCKS || (mode != 0 && mode != 1 && mode != 2 && mode != 4)) return GC_ERR_PARAM;
+    HIPCHK(c, hipSetDevice(c->device));
+    const GcMfGeom g = gc_mf_geom(n, frameBlocks, fast != 0);
+    const size_t cntBytes = (size_t)g.cntWords * sizeof(uint32_t), entBytes = (size_t)g.nFrames * g.frameBytes * sizeof(GcMfEntry), srcBytes = (n + 15u) & ~(size_t)15u;
+    void* d = nullptr;
+    HIPCHK(c, hipMalloc(&d, entBytes + cntBytes + srcBytes));
+    GcMfEntry* const dEnt = (GcMfEntry*)d; uint32_t* const dCnt = (uint32_t*)((uint8_t*)d + entBytes); uint8_t* const dSrc = (uint8_t*)d + entBytes + cntBytes;
+    const uint32_t perT = gc_xcd_per(g.nTiles), nParts = 1u << g.partLog;
+    hipStream_t st = c->stream;
+    hipError_t e = hipMemcpy(dSrc, src, n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(dEnt, 0xFF, entBytes, st);
+    if (e == hipSuccess) {
+#define MFT_LAUNCH(cntK, scatK) do { \
+        if (fast) { GC_LAUNCH(cntK##_p8, perT * GC_XCDS, nParts, st, (const uint8_t*)dSrc, (uint64_t)n, frameBlocks, g.nTiles, perT, dCnt); \
+                    GC_LAUNCH(gc_mf_scan_kernel_p8, g.nFrames, 1024, st, dCnt, g.tilesPerFrame); \
+                    GC_LAUNCH(scatK##_p8, perT * GC_XCDS, g.scatterT, st, (const uint8_t*)dSrc, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)dCnt, dEnt); } \
+        else      { GC_LAUNCH(cntK, perT * GC_XCDS, nParts, st, (const uint8_t*)dSrc, (uint64_t)n, frameBlocks, g.nTiles, perT, dCnt); \
+                    GC_LAUNCH(gc_mf_scan_kernel, g.nFrames, 1024, st, dCnt, g.tilesPerFrame); \
+                    GC_LAUNCH(scatK, perT * GC_XCDS, g.scatterT, st, (const uint8_t*)dSrc, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)dCnt, dEnt); } } while (0)
+        if (mode == 0) MFT_LAUNCH(gc_mf_count_kernel, gc_mf_scatter_kernel);
+        else if (mode == 1) MFT_LAUNCH(gc_mf_count_far_kernel, gc_mf_scatter_far_kernel);
+        else if (mode == 2) MFT_LAUNCH(gc_mf_count_short_kernel, gc_mf_scatter_short_kernel);
+        else MFT_LAUNCH(gc_mf_count_far2_kernel, gc_mf_scatter_far2_kernel);
+#undef MFT_LAUNCH
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(offs, dCnt, cntBytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(ent, dEnt, entBytes, hipMemcpyDeviceToHost);
+    hipFree(d);
+    if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "gc_test_mf_lists failed: %s", hipGetErrorString(e)); return GC_ERR_HIP; }
+    return GC_OK;
+}
 #endif
 
 extern "C" int gc_zstd_finish(gc_ctx* c, size_t* compressedSize)

@@ -25,6 +25,17 @@ struct __attribute__((aligned(16))) GcU4 { uint32_t x, y, z, w; };     // one gl
 __device__ __forceinline__ uint32_t gc_hibit32(uint32_t v) { return 31u - (uint32_t)__clz((int)v); }   // v != 0
 __device__ __forceinline__ uint32_t gc_ctz64(uint64_t v) { return (uint32_t)__ffsll((long long)v) - 1u; } // v != 0
 
+// Funnel shift: the low 32 bits of the 64-bit value hi:lo shifted right by sh & 31 -- one v_alignbit_b32 (a 64-bit shift is two instructions and a move on gfx950)
+__device__ __forceinline__ uint32_t gc_funnel_shr(uint32_t hi, uint32_t lo, uint32_t sh)
+{
+#ifdef HIPEMU
+    sh &= 31u;
+    return sh ? (lo >> sh) | (hi << (32u - sh)) : lo;
+#else
+    return __builtin_amdgcn_alignbit(hi, lo, sh);
+#endif
+}
+
 // LZMA distance slot of dist = distance - 1 (C/LzmaEnc.c GetPosSlot): 2 * floor(log2 dist) + next bit
 __device__ __forceinline__ uint32_t gc_dist_slot(uint32_t dist)
 {

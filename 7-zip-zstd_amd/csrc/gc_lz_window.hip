@@ -88,7 +88,7 @@ __device__ __forceinline__ void mf_stage(uint32_t* sW, uint32_t nWords, const ui
         sW[4u * c] = v.x; sW[4u * c + 1u] = v.y; sW[4u * c + 2u] = v.z; sW[4u * c + 3u] = v.w;
     }
 }
-// bytes i .. i+7 of the staged tile: three aligned LDS words + two funnel shifts (v_alignbit).  (Round 6 measured the obvious alternative: gfx950 accepts LDS reads at
+// bytes i .. i+7 of the staged tile: three aligned LDS words + two funnel shifts (v_alignbit_b32).  (Round 6 measured the obvious alternative: gfx950 accepts LDS reads at
 // any byte address and hipcc turns an unaligned 8-byte memcpy into ONE ds_read_b64 -- 19 % fewer instructions in the fused verify + parse kernel, the same bytes
 // out -- but the hardware serves a misaligned ds_read_b64 several times slower than three aligned words: W1 0.66 -> 1.97 ms, W3 3.25 -> 6.23 ms, the fused kernel
 // unchanged, zstd-L3 on 1 GB 45.3 -> 37.7 GB/s, run s1.  Aligned words it is.)
@@ -96,9 +96,7 @@ __device__ __forceinline__ uint64_t mf_lds_ld64(const uint32_t* sW, uint32_t i)
 {
     const uint32_t w = i >> 2, sh = (i & 3u) * 8u;
     const uint32_t w0 = sW[w], w1 = sW[w + 1u], w2 = sW[w + 2u];
-    const uint32_t lo = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh);
-    const uint32_t hi = (uint32_t)((((uint64_t)w2 << 32) | w1) >> sh);
-    return ((uint64_t)hi << 32) | lo;
+    return ((uint64_t)gc_funnel_shr(w2, w1, sh) << 32) | gc_funnel_shr(w1, w0, sh);
 }
 __device__ __forceinline__ uint32_t mf_lds_byte(const uint32_t* sW, uint32_t i) { return (sW[i >> 2] >> ((i & 3u) * 8u)) & 0xFFu; }
 
@@ -124,54 +122,102 @@ __device__ __forceinline__ uint32_t mf_lds_byte(const uint32_t* sW, uint32_t i) 
 // the same text (source trees, archives of similar files) the most recent position with the same 16 bytes is often a copy that diverges a few dozen bytes later, where the
 // reference's chains and trees return the LONGEST match (real sources, zstd level 9 and 19: 1.12 x the reference with 10 % more sequences of the same cost each).
 #define MF_FAR2  4
-struct MfKeys { bool ok, run; uint32_t part; uint64_t entry; };
-template <int MODE>
-__device__ __forceinline__ MfKeys mf_keys(const uint32_t* sW, uint32_t q, const MfTile& T)
+// Which positions of a tile are listed: tile-uniform, computed once per workgroup from scalar values.
+struct MfList {
+    uint32_t limit;                   // tile positions q < limit exist and have a full compare window left in the frame
+    uint32_t first;                   // the first tile position with a byte of the frame in front of it: 0, or 1 in the frame's first tile
+    uint32_t wTile;                   // frame-relative position of the tile's first byte
+};
+__device__ __forceinline__ MfList mf_list(const MfTile& T)
 {
-    MfKeys r; r.ok = false; r.run = false; r.part = 0; r.entry = 0;
-    const uint64_t P = T.tileStart + q;
-    const uint64_t x = mf_lds_ld64(sW, q + MF_STAGE_PAD);
-    if (P > T.frameStart) r.run = ((x << 8) | (uint64_t)mf_lds_byte(sW, q + MF_STAGE_PAD - 1u)) == x;
-    if (q < T.len && P + GC_MATCH_CAP + 16u <= T.frameEnd && !r.run) {
-        const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
-        uint32_t hL = lz_hash_long(lo, hi), hS = lz_hash_short(lo, hi);
-        if (MODE == MF_SHORT) {
-            // three equal bytes are not listed in this pass (round 5): the hottest 3-byte keys of machine code and tables (00 00 00, FF FF FF, CC CC CC) sit in ONE partition each,
-            // whose last list segment then is the tail of W4 -- 211.9 MB of shared objects at FLZMA2 level 5: this pass 16.5 -> 8.5 ms (the call 103.7 -> 95.5 ms) for +0.003 % size;
-            // such a position keeps what the other passes found and the near candidates of W5s
-            if (((lo ^ (lo >> 8)) & 0xFFFFu) == 0u) return r;
-            hS = (lo & 0xFFFFFFu) * 0x9E3779B1u; hS ^= hS >> 15; hS *= 0x2C1B3C6Du;     // bytes 0..2
-            hL = lo * 0x9E3779B1u; hL ^= hL >> 15; hL *= 0x85EBCA77u;                   // bytes 0..3
-        }
-        if (MODE == MF_FAR2) {
-            const uint64_t y = mf_lds_ld64(sW, q + MF_STAGE_PAD + 8u), z = mf_lds_ld64(sW, q + MF_STAGE_PAD + 16u), w = mf_lds_ld64(sW, q + MF_STAGE_PAD + 24u);
-            uint32_t h = hL + (uint32_t)y * 0xC2B2AE3Du; h ^= h >> 15; h *= 0x2C1B3C6Du;
-            h += (uint32_t)(y >> 32) * 0x27D4EB2Fu; h ^= h >> 13; h *= 0x165667B1u;
-            h += (uint32_t)z * 0x9E3779B1u; h ^= h >> 16; h *= 0x85EBCA6Bu;
-            hS = h + (uint32_t)(z >> 32) * 0xC2B2AE35u;           // bytes 0..23
-            hS ^= hS >> 15; hS *= 0x2C1B3C6Du;
-            hL = hS + (uint32_t)w * 0x27D4EB2Fu; hL ^= hL >> 13; hL *= 0x165667B1u;
-            hL += (uint32_t)(w >> 32) * 0x9E3779B1u;              // bytes 0..31
-            hL ^= hL >> 16; hL *= 0x85EBCA77u;
-        }
-        if (MODE == MF_FAR) {
-            const uint64_t y = mf_lds_ld64(sW, q + MF_STAGE_PAD + 8u);
-            const uint32_t lo1 = (uint32_t)y, hi1 = (uint32_t)(y >> 32);
-            hS = hL + lo1 * 0xC2B2AE3Du;                          // bytes 0..11
-            hS ^= hS >> 15; hS *= 0x2C1B3C6Du;
-            hL = hS + hi1 * 0x27D4EB2Fu;                          // bytes 0..15
-            hL ^= hL >> 13; hL *= 0x165667B1u;
-        }
-        r.ok = true;
-        r.part = hS >> (32u - GC_MF_PART_LOG);
-        r.entry = (uint64_t)(uint32_t)(P - T.frameStart)
-                | ((uint64_t)(hL >> (32u - GC_MF_KL_BITS)) << GC_MF_POS_BITS)
-                | ((uint64_t)((hS >> (32u - GC_MF_PART_LOG - GC_MF_KS_BITS)) & ((1u << GC_MF_KS_BITS) - 1u)) << (GC_MF_POS_BITS + GC_MF_KL_BITS));
+    MfList L;
+    const uint64_t room = T.frameEnd - T.tileStart;               // (meaningful where T.len != 0)
+    L.limit = 0u;
+    if (T.len != 0u && room >= GC_MATCH_CAP + 16u) L.limit = room - (GC_MATCH_CAP + 16u) + 1u < T.len ? (uint32_t)(room - (GC_MATCH_CAP + 16u) + 1u) : T.len;
+    L.first = T.tileStart > T.frameStart ? 0u : 1u;
+    L.wTile = (uint32_t)(T.tileStart - T.frameStart);
+    return L;
+}
+// THE listing predicate, the one place that states it: W1 counts, W3 places and W5 skips exactly the positions it accepts (W3 stays inside the runs W1 counted, and every
+// position gets a record, because all three ask here).  `same` = the 8 bytes at q equal the 8 bytes at q - 1 (mf_window).
+__device__ __forceinline__ bool mf_in_run(const MfList& L, uint32_t q, bool same) { return same && q >= L.first; }
+__device__ __forceinline__ bool mf_listed(const MfList& L, uint32_t q, bool same) { return q < L.limit && !mf_in_run(L, q, same); }
+
+// The 4 * NW bytes at LDS byte b + 1 as NW little-endian words x[], and whether the 8 bytes at b + 1 equal the 8 bytes at b.  With b = the LDS byte of position q - 1
+// (q + MF_STAGE_PAD - 1: the pad guarantees that its word exists) that is the position's window and its run test from NW + 1 aligned words: a[k] = bytes b + 4k ..
+// (one funnel shift each by the byte phase of b), x[k] = a[] one byte on (one funnel shift each by the constant 8; the last one takes its top byte from the last word
+// shifted down).  No read at an unaligned address, no 64-bit shift, nothing read twice.
+template <uint32_t NW>
+__device__ __forceinline__ bool mf_window(const uint32_t* sW, uint32_t b, uint32_t x[NW])
+{
+    const uint32_t* p = sW + (b >> 2);
+    const uint32_t sh = (b & 3u) * 8u;
+    uint32_t a[NW + 1u];
+#pragma unroll
+    for (uint32_t k = 0; k < NW; k++) a[k] = gc_funnel_shr(p[k + 1u], p[k], sh);
+    a[NW] = p[NW] >> sh;
+#pragma unroll
+    for (uint32_t k = 0; k < NW; k++) x[k] = gc_funnel_shr(a[k + 1u], a[k], 8u);
+    return ((a[0] ^ x[0]) | (a[1] ^ x[1])) == 0u;
+}
+
+// Keys of tile position q from its window x[] (MF_NW words) and its run test.  Every lane hashes: the caller predicates only its LDS atomic and its store on `ok`.
+// The entry comes in 32-bit halves: lo = pos | kL << POS_BITS, hi = the rest of kL | kS.
+#define MF_NW(MODE) ((MODE) == MF_FAR2 ? 8u : ((MODE) == MF_FAR ? 4u : 2u))
+struct MfKeys { bool ok; uint32_t part, lo, hi; };
+__device__ __forceinline__ GcMfEntry mf_entry(const MfKeys& k) { return ((uint64_t)k.hi << 32) | k.lo; }
+template <int MODE>
+__device__ __forceinline__ MfKeys mf_keys_of(const uint32_t x[MF_NW(MODE)], bool same, uint32_t q, const MfList& L)
+{
+    constexpr uint32_t NW = MF_NW(MODE);
+    MfKeys r;
+    r.ok = mf_listed(L, q, same);
+    const uint32_t lo = x[0], hi = x[1];
+    uint32_t hL = lz_hash_long(lo, hi), hS = lz_hash_short(lo, hi);
+    if (MODE == MF_SHORT) {
+        // three equal bytes are not listed in this pass (round 5): the hottest 3-byte keys of machine code and tables (00 00 00, FF FF FF, CC CC CC) sit in ONE partition each,
+        // whose last list segment then is the tail of W4 -- 211.9 MB of shared objects at FLZMA2 level 5: this pass 16.5 -> 8.5 ms (the call 103.7 -> 95.5 ms) for +0.003 % size;
+        // such a position keeps what the other passes found and the near candidates of W5s
+        r.ok = r.ok && ((lo ^ (lo >> 8)) & 0xFFFFu) != 0u;
+        hS = (lo & 0xFFFFFFu) * 0x9E3779B1u; hS ^= hS >> 15; hS *= 0x2C1B3C6Du;     // bytes 0..2
+        hL = lo * 0x9E3779B1u; hL ^= hL >> 15; hL *= 0x85EBCA77u;                   // bytes 0..3
     }
+    if (MODE == MF_FAR2) {
+        uint32_t h = hL + x[2 % NW] * 0xC2B2AE3Du; h ^= h >> 15; h *= 0x2C1B3C6Du;
+        h += x[3 % NW] * 0x27D4EB2Fu; h ^= h >> 13; h *= 0x165667B1u;
+        h += x[4 % NW] * 0x9E3779B1u; h ^= h >> 16; h *= 0x85EBCA6Bu;
+        hS = h + x[5 % NW] * 0xC2B2AE35u;                         // bytes 0..23
+        hS ^= hS >> 15; hS *= 0x2C1B3C6Du;
+        hL = hS + x[6 % NW] * 0x27D4EB2Fu; hL ^= hL >> 13; hL *= 0x165667B1u;
+        hL += x[7 % NW] * 0x9E3779B1u;                            // bytes 0..31
+        hL ^= hL >> 16; hL *= 0x85EBCA77u;
+    }
+    if (MODE == MF_FAR) {
+        hS = hL + x[2 % NW] * 0xC2B2AE3Du;                        // bytes 0..11
+        hS ^= hS >> 15; hS *= 0x2C1B3C6Du;
+        hL = hS + x[3 % NW] * 0x27D4EB2Fu;                        // bytes 0..15
+        hL ^= hL >> 13; hL *= 0x165667B1u;
+    }
+    r.part = hS >> (32u - GC_MF_PART_LOG);
+    const uint32_t kL = hL >> (32u - GC_MF_KL_BITS), kS = (hS >> (32u - GC_MF_PART_LOG - GC_MF_KS_BITS)) & ((1u << GC_MF_KS_BITS) - 1u);
+    static_assert(GC_MF_POS_BITS < 32u && GC_MF_POS_BITS + GC_MF_KL_BITS > 32u && GC_MF_POS_BITS + GC_MF_KL_BITS + GC_MF_KS_BITS <= 64u, "the long key straddles the halves of an entry");
+    r.lo = (L.wTile + q) | (kL << GC_MF_POS_BITS);
+    r.hi = (kL >> (32u - GC_MF_POS_BITS)) | (kS << (GC_MF_POS_BITS + GC_MF_KL_BITS - 32u));
     return r;
+}
+// ... with the window read here; b = the LDS byte of position q - 1 relative to sW (callers that walk the tile in constant steps fold the step into sW)
+template <int MODE>
+__device__ __forceinline__ MfKeys mf_keys(const uint32_t* sW, uint32_t b, uint32_t q, const MfList& L)
+{
+    uint32_t x[MF_NW(MODE)];
+    const bool same = mf_window<MF_NW(MODE)>(sW, b, x);
+    return mf_keys_of<MODE>(x, same, q, L);
 }
 
 // ------------------------------------------------------------------------------------------------ W1 count
+// A histogram does not care about order, so a lane takes FOUR consecutive positions from a 4-byte boundary on (W3 has to keep one position per lane and round): the
+// words are read once for the four, the byte phase of every window is a constant, and the run test compares a window with the lane's previous one.  Against one
+// position per lane through mf_keys, same session: 0.525 -> 0.372 ms on 1 GB (profiles/mf_keys.md).
 template <int MODE>
 __device__ __forceinline__ void mf_count_body(const uint8_t* __restrict__ src, uint64_t srcSize, uint32_t frameBlocks, uint32_t nTiles, uint32_t per, uint32_t* __restrict__ cnt)
 {
@@ -185,9 +231,24 @@ __device__ __forceinline__ void mf_count_body(const uint8_t* __restrict__ src, u
     sHist[t] = 0;
     if (T.len) mf_stage(sW, MF_STAGE_WORDS, src, srcSize, T.tileStart, t, MF_T);
     __syncthreads();
-    for (uint32_t q = t; q < T.len; q += MF_T) {
-        const MfKeys k = mf_keys<MODE>(sW, q, T);
-        if (k.ok) atomicAdd(&sHist[k.part], 1u);
+    const MfList L = mf_list(T);
+    constexpr uint32_t NW = MF_NW(MODE);
+    for (uint32_t q0 = 4u * t; q0 < L.limit; q0 += 4u * MF_T) {
+        const uint32_t* p = sW + (q0 + MF_STAGE_PAD) / 4u - 1u;   // the word in front of position q0's
+        uint32_t w[NW + 2u];
+#pragma unroll
+        for (uint32_t k = 0; k < NW + 2u; k++) w[k] = p[k];
+        uint32_t prev0 = gc_funnel_shr(w[1], w[0], 24u), prev1 = gc_funnel_shr(w[2], w[1], 24u);      // the window of position q0 - 1
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; j++) {
+            uint32_t x[NW];
+#pragma unroll
+            for (uint32_t k = 0; k < NW; k++) x[k] = j ? gc_funnel_shr(w[k + 2u], w[k + 1u], 8u * j) : w[k + 1u];
+            const bool same = x[0] == prev0 && x[1] == prev1;
+            prev0 = x[0]; prev1 = x[1];
+            const MfKeys k = mf_keys_of<MODE>(x, same, q0 + j, L);
+            if (k.ok) atomicAdd(&sHist[k.part], 1u);
+        }
     }
     __syncthreads();
     cnt[((uint64_t)T.frame * (TPF + 1u) + T.tif) * GC_MF_PARTS + t] = sHist[t];
@@ -269,9 +330,11 @@ MFK(gc_mf_scan_kernel)(uint32_t* __restrict__ cnt, uint32_t tilesPerFrame)
 // positions in registers, 16 bits each, for pass B to rank by; and in the output loop, which rebuilds the 8-byte entry from the
 // staged bytes (keeping the entries would take 8 bytes of LDS per position).  Pass B reads no input bytes and hashes nothing.
 //
-// Fast geometry: 512 threads per 8 KiB tile, 48 VGPRs, 33 872 B of LDS -> four workgroups = all 32 wave slots of a CU (with one thread per
+// Fast geometry: 512 threads per 8 KiB tile, 47 VGPRs, 33 872 B of LDS -> four workgroups = all 32 wave slots of a CU (with one thread per
 // partition, 256, it was 30 800 B: five workgroups, 20 waves).  The wide geometry keeps 1024 threads per 16 KiB tile.
 // zstd level 3 on 1 GB, one MI355X, both in one session: 3.13 -> 2.57 ms, the traffic (9.1 GB counted) is untouched (profiles/scatter_full_cu.md).
+// The key evaluations were what bound it then (83 vector instructions per round of 64 positions by counter, 88 % of the SIMDs' cycles); with mf_window / mf_keys_of
+// they are 49 and the kernel 2.38 ms: ten LDS instructions per position are now the busiest unit (profiles/mf_keys.md).
 template <int MODE>
 __device__ __forceinline__ void mf_scatter_body(const uint8_t* __restrict__ src, uint64_t srcSize, uint32_t frameBlocks, uint32_t nTiles, uint32_t per,
                      const uint32_t* __restrict__ offs, GcMfEntry* __restrict__ ent)
@@ -290,12 +353,13 @@ __device__ __forceinline__ void mf_scatter_body(const uint8_t* __restrict__ src,
     for (uint32_t i = t; i < MFS_WAVES * GC_MF_PARTS; i += MFS_T) (&sRun[0][0])[i] = 0;
     mf_stage(sW, MF_STAGE_WORDS, src, srcSize, T.tileStart, t, MFS_T);
     __syncthreads();
+    const MfList L = mf_list(T);
     const uint32_t qBase = wave * (GC_MF_TILE / MFS_WAVES);
     // pass A: per-wave histograms; pk: partition of the position of round r, 0xFFFF = not listed (two rounds per register)
     uint32_t pk[MFS_ROUNDS / 2u];
 #pragma unroll
     for (uint32_t r = 0; r < MFS_ROUNDS; r++) {
-        const MfKeys k = mf_keys<MODE>(sW, qBase + r * 64u + lane, T);
+        const MfKeys k = mf_keys<MODE>(sW + r * 16u, qBase + lane + MF_STAGE_PAD - 1u, qBase + r * 64u + lane, L);     // (the round's 64 bytes folded into the base: one address per thread)
         const uint32_t p = k.ok ? k.part : 0xFFFFu;
         pk[r >> 1] = (r & 1u) ? (pk[r >> 1] | (p << 16)) : p;
         if (k.ok) atomicAdd(&sRun[wave][k.part], 1u);
@@ -332,8 +396,10 @@ __device__ __forceinline__ void mf_scatter_body(const uint8_t* __restrict__ src,
     // output: slot j of the sorted tile -> its partition's run in HBM
     GcMfEntry* E = ent + (uint64_t)T.frame * ((uint64_t)MF_F(frameBlocks) * GC_ZSTD_BLOCK_MAX);
     for (uint32_t j = t; j < nEnt; j += MFS_T) {
-        const MfKeys k = mf_keys<MODE>(sW, sPerm[j], T);
-        E[sDelta[k.part] + j] = k.entry;
+        const uint32_t q = sPerm[j];
+        const MfKeys k = mf_keys<MODE>(sW, q + MF_STAGE_PAD - 1u, q, L);
+        // (a byte offset of 32 bits on the uniform base: entry indices stay below 2^24)
+        *(GcMfEntry*)((uint8_t*)E + (uint32_t)((sDelta[k.part] + j) << 3)) = mf_entry(k);
     }
 }
 extern "C" __global__ void __launch_bounds__(MFS_T)
@@ -620,13 +686,14 @@ __device__ __forceinline__ void mf_verify_tile(const MfTile& T, const uint8_t* _
     const uint32_t pTile = (uint32_t)(T.tileStart - blockBase);
     const uint32_t wTile = (uint32_t)(T.tileStart - T.frameStart);
     // unlisted positions: byte runs match at distance 1, the tail of the frame does not match at all
+    const MfList L = mf_list(T);
     auto unlisted = [&]() {
         for (uint32_t q = t; q < T.len; q += MFV_T) {
             if (!FAR && sRec[q] != MFV_NONE) continue;              // a listed position: its record is in place (nineteen in twenty on text)
-            const uint64_t x = mf_lds_ld64(sW, q + MF_STAGE_PAD);
-            const bool run = T.tileStart + q > T.frameStart && ((x << 8) | (uint64_t)mf_lds_byte(sW, q + MF_STAGE_PAD - 1u)) == x;
-            const bool windowed = T.tileStart + q + GC_MATCH_CAP + 16u <= T.frameEnd;
-            if (windowed && !run) continue;                       // listed
+            uint32_t x[2];
+            const bool same = mf_window<2u>(sW, q + MF_STAGE_PAD - 1u, x);
+            if (mf_listed(L, q, same)) continue;
+            const bool run = mf_in_run(L, q, same), windowed = q < L.limit;
             const uint32_t p = pTile + q;
             uint32_t len = 0;
             if (run && windowed && p + 8u <= nBlk) {              // both sides of the compare lie in the staged tile
