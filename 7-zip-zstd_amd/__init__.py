@@ -499,6 +499,49 @@ class Flzma2Encoder(_EncoderBase):
         self._check(self._lib.gc_flzma2_last_timing(self._ctx, ms), "gc_flzma2_last_timing")
         return dict(zip(self.KERNELS, [float(x) for x in ms]))
 
+    RC_STRIDE = 4096 + 1024               # GC_LZMA_RC_STRIDE: staging bytes per 4 KiB rc chunk
+
+    @staticmethod
+    def stream_words(seg_log):
+        """GC_LZMA_STREAM_WORDS: the words a model segment of 2^seg_log bytes has to itself"""
+        return (9 << seg_log) + 64
+
+    def code_parsed_device(self, d_src_ptr, n, d_dst_ptr, dst_cap, blocks, win_cost=None, flags=0):
+        """TEST BUILDS ONLY (csrc/libgpucodec_hooks.so, the emulator library): the stream call with the match finder replaced by a stated parse (gc_api.hip
+        gc_test_flzma2_encode_parsed).  blocks: per 128 KiB block of the n bytes at d_src_ptr a pair (number of literals, records) -- records a (k, 2) uint32 array of
+        K1's records, [literals in front of the match, offset << 8 | match length (1..255)]; a match longer than 255 is a chain of records of one offset with no
+        literals between them (tests/lzma2_parse.py derives them).  win_cost: None, or 32 uint32 per block, the parse's estimate per 4 KiB window in 1/16 bit.  The
+        library refuses a parse that does not tile its block or reaches in front of its frame; finish() reads the size as usual."""
+        import numpy as np
+        fn = getattr(self._lib, "gc_test_flzma2_encode_parsed", None)
+        if fn is None:
+            raise GpuCodecError("gc_test_flzma2_encode_parsed: this library is not a test build")
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
+        fn.restype = C.c_int
+        recs = [np.ascontiguousarray(r, dtype=np.uint32).reshape(-1, 2) for _, r in blocks]
+        meta = np.array([[r.shape[0], int(nl)] for (nl, _), r in zip(blocks, recs)], dtype=np.uint32).reshape(-1, 2)
+        rec = np.ascontiguousarray(np.concatenate(recs + [np.zeros((1, 2), np.uint32)]))
+        wc = None if win_cost is None else np.ascontiguousarray(win_cost, dtype=np.uint32).ravel()
+        if wc is not None and wc.size != 32 * len(blocks):
+            raise ValueError("win_cost: 32 words per block")
+        self._check(fn(self._ctx, d_src_ptr, n, d_dst_ptr, dst_cap, self.level, int(flags), rec.ctypes.data, meta.ctypes.data, None if wc is None else wc.ctypes.data),
+                    "gc_test_flzma2_encode_parsed")
+
+    def rc_words(self, words, chunks, seg_log):
+        """TEST BUILDS ONLY: the two range-coder kernels (gc_api.hip gc_test_lzma2_rc_words) on the (probability, bit) words of whole segments (uint16, stream_words(seg_log)
+        per segment) and a chunk table ((nRc, 4) uint32: usize, csize, wordStart, wordEnd) -> (staging bytes (nRc, RC_STRIDE) uint8, csize per chunk uint32)."""
+        import numpy as np
+        fn = getattr(self._lib, "gc_test_lzma2_rc_words", None)
+        if fn is None:
+            raise GpuCodecError("gc_test_lzma2_rc_words: this library is not a test build")
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        fn.restype = C.c_int
+        w = np.ascontiguousarray(words, dtype=np.uint16).ravel()
+        ci = np.ascontiguousarray(chunks, dtype=np.uint32).reshape(-1, 4)
+        out, cs = np.zeros((ci.shape[0], self.RC_STRIDE), np.uint8), np.zeros(ci.shape[0], np.uint32)
+        self._check(fn(self._ctx, w.ctypes.data, w.size, ci.ctypes.data, ci.shape[0], int(seg_log), out.ctypes.data, cs.ctypes.data), "gc_test_lzma2_rc_words")
+        return out, cs
+
 
 class BrotliEncoder(_EncoderBase):
     CODEC = 2

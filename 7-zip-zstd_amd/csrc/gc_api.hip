@@ -1166,6 +1166,94 @@ extern "C" size_t gc_flzma2_compress_bound(size_t n)
 // Matches never reach back further than the start of their frame: 128 KiB (p = 10) or 8 MiB (p = 22).
 extern "C" unsigned char gc_flzma2_dict_prop(int level) { const uint32_t f = flzma2_frame_blocks(level); return f == 1u ? 10 : (f > GC_MF_MAX_FRAME_BLOCKS ? 24 : 22); }      // 128 KiB / 8 MiB / 16 MiB
 
+// The back end of the FLZMA2 stream call -- L1 (item lists), L2 (model), L3a / L3b (range coder), segment kinds, plan and emit -- shared with the test entries
+// gc_test_flzma2_encode_parsed and gc_test_lzma2_rc_words (below), so that what the tests feed an exact parse, or exact (probability, bit) words, runs the product's
+// launches and nothing else.  GcFlzma2Stage: what those launches take besides the data, derived from the level and the test hooks in ONE place.
+struct GcFlzma2Stage { uint32_t segLog, segPerBlock, mergeWords, wordCap, rep4, litSel, segMerge, mergeBudget; };
+static GcFlzma2Stage flzma2_stage(int level, uint32_t nBlocks, uint32_t groupBlocks)
+{
+    GcFlzma2Stage s;
+    s.segLog = flzma2_seg_log(level);
+    s.segPerBlock = GC_ZSTD_BLOCK_MAX >> s.segLog;
+    s.mergeWords = level <= 6 ? 32768u : GC_LZMA_RC_MERGE_WORDS;                               // coded bits of one LZMA2 chunk = the chain of ONE lane of L3.  Levels <= 6 (run s9, 211.9 MB): 49 152 -> 32 768 words takes 1.65 ms off L3
+                                                                                               // (5.98 -> 4.33) for +0.06 % size (10 bytes of header and coder flush per chunk)
+    s.rep4 = 1;                                                                                // rep2 / rep3 coding in L2 (gc_lzma2_enc.hip LzLru); test hook: 0 = rep0 / rep1 only
+    gc_env_u32("GC_L2_REP4", 0u, 1u, &s.rep4);
+    s.litSel = 1;                                                                              // lc / lp per model segment (gc_lzma2_model_kernel); 0 = the reference's lc 3 / lp 0 everywhere
+    s.wordCap = GC_LZMA_STREAM_WORDS(s.segLog);                                                // words a segment may produce before it is stored instead
+    gc_env_u32("GC_SEG_WORD_CAP", 1u, GC_LZMA_STREAM_WORDS(s.segLog), &s.wordCap);              // test hook: a low cap sends ordinary segments down that path
+    // model segments over 2 / 4 / 8 blocks where the parse prices them within what one block of poorly compressible data costs (gc_lzma2_model_kernel): level >= 5.
+    // Parts (test hook) are whole frames, frames are multiples of eight blocks: a group never straddles a part.
+    s.segMerge = (s.segLog == 17u && level >= 5 && s.rep4) ? 8u : 0u;
+    gc_env_u32("GC_SEG_MERGE", 0u, 8u, &s.segMerge);                                            // test hook: 0 = every block a segment of its own (round 4)
+    if (s.segMerge & (s.segMerge - 1u)) s.segMerge = 4u;
+    while (s.segMerge > 1u && nBlocks > groupBlocks && (groupBlocks % s.segMerge) != 0u) s.segMerge >>= 1;      // (groups are aligned to the input: they must not straddle frames, or a frame-aligned shard would differ from the whole input's bytes)
+    s.mergeBudget = 16u * 655360u;                                                             // 640 Ki coded bits (1/16 bit units) = 5 bits per byte of ONE 128 KiB block.  Measured on 211.9 MB (run s9, model kernel / size):
+                                                                                               // 896 Ki -- the longest chain the launch has anyway, PCM-like data -- 17.0 ms on the Silesia stand-in and 21.5 ms on shared objects
+                                                                                               // (the estimate is the PARSE's: the model's chain comes out longer); 640 Ki 14.4 / 14.5 ms, as without merging, for +0.01 / +0.05 % size
+    return s;
+}
+// (p, bit) stream between the model kernel and the range coder: 2 bytes per coded bit, <= 9 coded bits per input byte; item lists; range-coder staging
+static int flzma2_reserve(gc_ctx* c, uint32_t nBlocks, uint32_t segLog)
+{
+    const uint32_t nSegs = nBlocks * (GC_ZSTD_BLOCK_MAX >> segLog), nRc = nBlocks * GC_LZMA_RC_PER_BLOCK;
+    const size_t needStream = (size_t)nSegs * GC_LZMA_STREAM_WORDS(segLog) * sizeof(uint16_t);
+    const size_t needM = (size_t)nBlocks * GC_LZMA_MAX_ITEMS * sizeof(uint64_t), needRc = (size_t)nRc * GC_LZMA_RC_STRIDE;
+    const GcWsNeed rows[] = { { c->lzStream, needStream, "LZMA stream" }, { c->lzM, needM, "LZMA items" }, { c->lzRcOut, needRc, "range-coder staging" } };
+    return mf_reserve(c, rows, 3);
+}
+// L3a + L3b over the rc chunks [rc0, rc0 + pRc) (whole blocks) on stream st
+static int flzma2_range_code(gc_ctx* c, hipStream_t st, uint32_t segLog, uint32_t rc0, uint32_t pRc)
+{
+    uint16_t* const words = c->lzStream + (size_t)(rc0 >> (segLog - GC_LZMA_RC_LOG)) * GC_LZMA_STREAM_WORDS(segLog);
+    GC_LAUNCH(gc_lzma2_rc_kernel, (pRc + 63u) / 64u, 64, st, words, segLog, pRc, c->lzRcOut + (size_t)rc0 * GC_LZMA_RC_STRIDE, c->lzInfo + rc0);
+    GC_LAUNCH(gc_lzma2_rc_fin_kernel, pRc, 64, st, (const uint16_t*)words, segLog, pRc, c->lzRcOut + (size_t)rc0 * GC_LZMA_RC_STRIDE, c->lzInfo + rc0);
+    return GC_OK;
+}
+// What follows the finder for part p (pBlocks blocks from blk0, pn bytes at psrc): L1 on the main stream behind evPart[p][1], L2 on stream2, L3 on stream3.
+// winCost: the parse's window costs of the part's first block, or nullptr
+static int flzma2_code_part(gc_ctx* c, const GcFlzma2Stage& s, uint32_t p, const uint8_t* psrc, size_t pn, uint32_t blk0, uint32_t pBlocks, const uint32_t* winCost)
+{
+    const uint32_t segLog = s.segLog, segPerBlock = s.segPerBlock, pSegs = pBlocks * segPerBlock, pRc = pBlocks * GC_LZMA_RC_PER_BLOCK;
+    hipEvent_t* ev = c->evPart[p];
+    GC_LAUNCH(gc_lzma2_prep_kernel, pBlocks, 256, c->stream, (const GcSeqRaw*)(c->seqRaw + (size_t)blk0 * GC_MAX_SEQ_PER_BLOCK),
+              (const GcBlockMeta*)(c->meta + blk0), (uint64_t)pn, c->lzM + (size_t)blk0 * GC_LZMA_MAX_ITEMS, c->lzNM + blk0);
+    HIPCHK(c, hipEventRecord(ev[2], c->stream));
+    // stage 2 (stream2): model
+    HIPCHK(c, hipStreamWaitEvent(c->stream2, ev[2], 0));
+    HIPCHK(c, hipEventRecord(ev[3], c->stream2));
+    GC_LAUNCH(gc_lzma2_model_kernel, pSegs, 64, c->stream2, psrc, (uint64_t)pn, (const uint64_t*)(c->lzM + (size_t)blk0 * GC_LZMA_MAX_ITEMS),
+              (const uint32_t*)(c->lzNM + blk0), segLog, (uint32_t)(blk0 != 0u ? 1u : 0u),
+              c->lzStream + (size_t)blk0 * segPerBlock * GC_LZMA_STREAM_WORDS(segLog), c->lzInfo + (size_t)blk0 * GC_LZMA_RC_PER_BLOCK,
+              winCost, c->profOn ? (unsigned long long*)c->prof : nullptr, s.mergeWords, s.wordCap, s.rep4, c->lzProps + (size_t)blk0 * segPerBlock, s.litSel, s.segMerge, s.mergeBudget);
+    HIPCHK(c, hipEventRecord(ev[4], c->stream2));
+    // stage 3 (stream3): range coder
+    HIPCHK(c, hipStreamWaitEvent(c->stream3, ev[4], 0));
+    HIPCHK(c, hipEventRecord(ev[5], c->stream3));
+    const int rc = flzma2_range_code(c, c->stream3, segLog, blk0 * GC_LZMA_RC_PER_BLOCK, pRc);
+    if (rc != GC_OK) return rc;
+    HIPCHK(c, hipEventRecord(ev[6], c->stream3));
+    return GC_OK;
+}
+// all parts coded -> headers and assembly on the main stream
+static int flzma2_join_and_emit(gc_ctx* c, const GcFlzma2Stage& s, const uint8_t* src, void* d_dst, size_t dstCap, uint32_t nBlocks, uint32_t nParts, unsigned flags)
+{
+    const uint32_t segLog = s.segLog, nSegs = nBlocks * s.segPerBlock, nRc = nBlocks * GC_LZMA_RC_PER_BLOCK;
+    uint8_t* const segKind = c->lzProps + (size_t)c->capBlocks * (GC_ZSTD_BLOCK_MAX >> GC_LZMA_SEG_LOG_MIN);
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->evPart[nParts - 1u][6], 0));
+    HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+    GC_LAUNCH(gc_lzma2_segkind_kernel, (nSegs + 255u) / 256u, 256, c->stream, (const GcLzmaChunkInfo*)c->lzInfo, (const uint8_t*)c->lzProps, nSegs, segLog, segKind);
+    GC_LAUNCH(gc_lzma2_plan_kernel, 1, 1024, c->stream, (const GcLzmaChunkInfo*)c->lzInfo, nRc, segLog, (uint64_t)dstCap, (uint32_t)flags, c->lzPlan, c->result,
+              (const uint8_t*)c->lzProps, (const uint8_t*)segKind);
+    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+    GC_LAUNCH(gc_lzma2_emit_kernel, nRc + 1u, 256, c->stream, src, segLog, (const uint8_t*)c->lzRcOut, (const GcLzmaChunkInfo*)c->lzInfo,
+              (const GcLzmaPlan*)c->lzPlan, nRc, (uint32_t)flags, (const uint64_t*)c->result, (uint8_t*)d_dst, (const uint8_t*)c->lzProps);
+    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+    HIPCHK(c, hipGetLastError());
+    c->pending = true; c->timed = true; c->lastCodec = 1;
+    return GC_OK;
+}
+
 extern "C" int gc_flzma2_compress_device(gc_ctx* c, const void* d_src, size_t n, void* d_dst, size_t dstCap, int level, unsigned flags)
 {
     if (!c || (!d_src && n) || !d_dst) return GC_ERR_PARAM;
@@ -1184,16 +1272,8 @@ extern "C" int gc_flzma2_compress_device(gc_ctx* c, const void* d_src, size_t n,
     const uint32_t nBlocks = gc_num_blocks(n);
     int rc = ensure_workspace(c, nBlocks);
     if (rc != GC_OK) return rc;
-    const uint32_t segLog = flzma2_seg_log(level);
-    const uint32_t nSegs = nBlocks * (GC_ZSTD_BLOCK_MAX >> segLog), nRc = nBlocks * GC_LZMA_RC_PER_BLOCK;
     const uint8_t* src = (const uint8_t*)d_src;
-    {   // (p, bit) stream between the model kernel and the range coder: 2 bytes per coded bit, <= 9 coded bits per input byte;
-        // item lists; range-coder staging
-        const size_t needStream = (size_t)nSegs * GC_LZMA_STREAM_WORDS(segLog) * sizeof(uint16_t);
-        const size_t needM = (size_t)nBlocks * GC_LZMA_MAX_ITEMS * sizeof(uint64_t), needRc = (size_t)nRc * GC_LZMA_RC_STRIDE;
-        const GcWsNeed rows[] = { { c->lzStream, needStream, "LZMA stream" }, { c->lzM, needM, "LZMA items" }, { c->lzRcOut, needRc, "range-coder staging" } };
-        if ((rc = mf_reserve(c, rows, 3)) != GC_OK) return rc;
-    }
+    if ((rc = flzma2_reserve(c, nBlocks, flzma2_seg_log(level))) != GC_OK) return rc;
     const GcLzPlan plan = with_hooks(flzma2_plan(level));
     const uint32_t fArg = lz_frame_arg(GC_CODEC_FLZMA2, level, nBlocks, c->dbgFrameBlocks);    // what the finder takes: overlapping frames from level 5
     const uint32_t groupBlocks = MF_C(fArg);
@@ -1214,24 +1294,7 @@ extern "C" int gc_flzma2_compress_device(gc_ctx* c, const void* d_src, size_t n,
         if (rc != GC_OK) return rc;
     }
     c->mfTimed = false; c->nParts = nParts;
-    const uint32_t segPerBlock = GC_ZSTD_BLOCK_MAX >> segLog;
-    const uint32_t mergeWords = level <= 6 ? 32768u : GC_LZMA_RC_MERGE_WORDS;                  // coded bits of one LZMA2 chunk = the chain of ONE lane of L3.  Levels <= 6 (run s9, 211.9 MB): 49 152 -> 32 768 words takes 1.65 ms off L3
-                                                                                               // (5.98 -> 4.33) for +0.06 % size (10 bytes of header and coder flush per chunk)
-    uint32_t rep4 = 1;                                                                         // rep2 / rep3 coding in L2 (gc_lzma2_enc.hip LzLru); test hook: 0 = rep0 / rep1 only
-    gc_env_u32("GC_L2_REP4", 0u, 1u, &rep4);
-    const uint32_t litSel = 1;                                                                 // lc / lp per model segment (gc_lzma2_model_kernel); 0 = the reference's lc 3 / lp 0 everywhere
-    uint32_t wordCap = GC_LZMA_STREAM_WORDS(segLog);                                           // words a segment may produce before it is stored instead
-    gc_env_u32("GC_SEG_WORD_CAP", 1u, GC_LZMA_STREAM_WORDS(segLog), &wordCap);                  // test hook: a low cap sends ordinary segments down that path
-    // model segments over 2 / 4 / 8 blocks where the parse prices them within what one block of poorly compressible data costs (gc_lzma2_model_kernel): level >= 5.
-    // Parts (test hook) are whole frames, frames are multiples of eight blocks: a group never straddles a part.
-    uint32_t segMerge = (segLog == 17u && level >= 5 && rep4) ? 8u : 0u;
-    gc_env_u32("GC_SEG_MERGE", 0u, 8u, &segMerge);                                              // test hook: 0 = every block a segment of its own (round 4)
-    if (segMerge & (segMerge - 1u)) segMerge = 4u;
-    while (segMerge > 1u && nBlocks > groupBlocks && (groupBlocks % segMerge) != 0u) segMerge >>= 1;      // (groups are aligned to the input: they must not straddle frames, or a frame-aligned shard would differ from the whole input's bytes)
-    const uint32_t mergeBudget = 16u * 655360u;                                                // 640 Ki coded bits (1/16 bit units) = 5 bits per byte of ONE 128 KiB block.  Measured on 211.9 MB (run s9, model kernel / size):
-                                                                                               // 896 Ki -- the longest chain the launch has anyway, PCM-like data -- 17.0 ms on the Silesia stand-in and 21.5 ms on shared objects
-                                                                                               // (the estimate is the PARSE's: the model's chain comes out longer); 640 Ki 14.4 / 14.5 ms, as without merging, for +0.01 / +0.05 % size
-    uint8_t* const segKind = c->lzProps + (size_t)c->capBlocks * (GC_ZSTD_BLOCK_MAX >> GC_LZMA_SEG_LOG_MIN);
+    const GcFlzma2Stage stage = flzma2_stage(level, nBlocks, groupBlocks);
     if (c->profOn) { HIPCHK(c, hipMemsetAsync(c->prof, 0, (GC_LZ_PHASES + GC_SEQ_PHASES) * sizeof(unsigned long long), c->stream)); c->profBlocks = 1u; }   // L2 phase sums (raw)
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
     uint32_t f0 = 0;
@@ -1240,50 +1303,140 @@ extern "C" int gc_flzma2_compress_device(gc_ctx* c, const void* d_src, size_t n,
         const uint32_t blk0 = f0 * groupBlocks, blk1 = f1 * groupBlocks < nBlocks ? f1 * groupBlocks : nBlocks;
         const uint64_t off = (uint64_t)blk0 * GC_ZSTD_BLOCK_MAX;
         const size_t pn = (size_t)(((uint64_t)blk1 * GC_ZSTD_BLOCK_MAX < n ? (uint64_t)blk1 * GC_ZSTD_BLOCK_MAX : (uint64_t)n) - off);
-        const uint32_t pBlocks = blk1 - blk0, pSegs = pBlocks * segPerBlock, pRc = pBlocks * GC_LZMA_RC_PER_BLOCK;
-        hipEvent_t* ev = c->evPart[p];
         // stage 1 (main stream): match finder + item lists
-        HIPCHK(c, hipEventRecord(ev[0], c->stream));
+        HIPCHK(c, hipEventRecord(c->evPart[p][0], c->stream));
         rc = launch_finder_part(c, plan, c->stream, p, src + off, pn, fArg, blk0, nullptr);
         if (rc != GC_OK) return rc;
-        HIPCHK(c, hipEventRecord(ev[1], c->stream));
-        GC_LAUNCH(gc_lzma2_prep_kernel, pBlocks, 256, c->stream, (const GcSeqRaw*)(c->seqRaw + (size_t)blk0 * GC_MAX_SEQ_PER_BLOCK),
-                  (const GcBlockMeta*)(c->meta + blk0), (uint64_t)pn, c->lzM + (size_t)blk0 * GC_LZMA_MAX_ITEMS, c->lzNM + blk0);
-        HIPCHK(c, hipEventRecord(ev[2], c->stream));
-        // stage 2 (stream2): model
-        HIPCHK(c, hipStreamWaitEvent(c->stream2, ev[2], 0));
-        HIPCHK(c, hipEventRecord(ev[3], c->stream2));
-        GC_LAUNCH(gc_lzma2_model_kernel, pSegs, 64, c->stream2, src + off, (uint64_t)pn, (const uint64_t*)(c->lzM + (size_t)blk0 * GC_LZMA_MAX_ITEMS),
-                  (const uint32_t*)(c->lzNM + blk0), segLog, (uint32_t)(off != 0u ? 1u : 0u),
-                  c->lzStream + (size_t)blk0 * segPerBlock * GC_LZMA_STREAM_WORDS(segLog), c->lzInfo + (size_t)blk0 * GC_LZMA_RC_PER_BLOCK,
-                  (const uint32_t*)((plan.priceParse && MF_F(fArg) > 1u) ? c->mfWinCost + (size_t)blk0 * 32u : nullptr),
-                  c->profOn ? (unsigned long long*)c->prof : nullptr, mergeWords, wordCap, rep4, c->lzProps + (size_t)blk0 * segPerBlock, litSel, segMerge, mergeBudget);
-        HIPCHK(c, hipEventRecord(ev[4], c->stream2));
-        // stage 3 (stream3): range coder
-        HIPCHK(c, hipStreamWaitEvent(c->stream3, ev[4], 0));
-        HIPCHK(c, hipEventRecord(ev[5], c->stream3));
-        GC_LAUNCH(gc_lzma2_rc_kernel, (pRc + 63u) / 64u, 64, c->stream3, c->lzStream + (size_t)blk0 * segPerBlock * GC_LZMA_STREAM_WORDS(segLog),
-                  segLog, pRc, c->lzRcOut + (size_t)blk0 * GC_LZMA_RC_PER_BLOCK * GC_LZMA_RC_STRIDE, c->lzInfo + (size_t)blk0 * GC_LZMA_RC_PER_BLOCK);
-        GC_LAUNCH(gc_lzma2_rc_fin_kernel, pRc, 64, c->stream3, (const uint16_t*)(c->lzStream + (size_t)blk0 * segPerBlock * GC_LZMA_STREAM_WORDS(segLog)),
-                  segLog, pRc, c->lzRcOut + (size_t)blk0 * GC_LZMA_RC_PER_BLOCK * GC_LZMA_RC_STRIDE, c->lzInfo + (size_t)blk0 * GC_LZMA_RC_PER_BLOCK);
-        HIPCHK(c, hipEventRecord(ev[6], c->stream3));
+        HIPCHK(c, hipEventRecord(c->evPart[p][1], c->stream));
+        rc = flzma2_code_part(c, stage, p, src + off, pn, blk0, blk1 - blk0,
+                              (const uint32_t*)((plan.priceParse && MF_F(fArg) > 1u) ? c->mfWinCost + (size_t)blk0 * 32u : nullptr));
+        if (rc != GC_OK) return rc;
         f0 = f1;
     }
     c->mfTimed = MF_F(fArg) > 1u; c->mfParts = nParts; c->mfPriced = c->mfTimed && plan.priceParse != 0u;
-    // all parts coded -> headers and assembly on the main stream
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->evPart[nParts - 1u][6], 0));
-    HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-    GC_LAUNCH(gc_lzma2_segkind_kernel, (nSegs + 255u) / 256u, 256, c->stream, (const GcLzmaChunkInfo*)c->lzInfo, (const uint8_t*)c->lzProps, nSegs, segLog, segKind);
-    GC_LAUNCH(gc_lzma2_plan_kernel, 1, 1024, c->stream, (const GcLzmaChunkInfo*)c->lzInfo, nRc, segLog, (uint64_t)dstCap, (uint32_t)flags, c->lzPlan, c->result,
-              (const uint8_t*)c->lzProps, (const uint8_t*)segKind);
-    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-    GC_LAUNCH(gc_lzma2_emit_kernel, nRc + 1u, 256, c->stream, src, segLog, (const uint8_t*)c->lzRcOut, (const GcLzmaChunkInfo*)c->lzInfo,
-              (const GcLzmaPlan*)c->lzPlan, nRc, (uint32_t)flags, (const uint64_t*)c->result, (uint8_t*)d_dst, (const uint8_t*)c->lzProps);
-    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+    return flzma2_join_and_emit(c, stage, src, d_dst, dstCap, nBlocks, nParts, flags);
+}
+
+#ifdef GC_TEST_HOOKS
+// Test entry (the test builds only; not part of include/gpucodec.h): the FLZMA2 stream call with the match finder replaced by a parse the caller states, so that a test
+// decides exactly which items L1, L2 and L3 get.  d_src / d_dst: device memory, as in gc_flzma2_compress_device.  seq / meta: HOST memory, what K1 leaves per block
+// (gc_common.h), packed -- block b's records follow block b - 1's, meta[b] counts them and the block's literals.  winCost: HOST memory, 32 words per block (the parse's
+// estimate per 4 KiB window in 1/16 bit; what hopeless segments and merged segments are decided by), or null: the model kernel then gets nullptr as for a plan without a
+// priced parse.  The parse is checked here, on the host, before anything is launched; a record of length 1 or 2 is legal (L1 / L2 make a short repeat, a literal or a
+// two-byte match of it).  (That the parse REPRODUCES the input is the caller's business.)  gc_flzma2_finish reads the result.
+extern "C" int gc_test_flzma2_encode_parsed(gc_ctx* c, const void* d_src, size_t n, void* d_dst, size_t dstCap, int level, unsigned flags,
+                                            const GcSeqRaw* seq, const GcBlockMeta* meta, const uint32_t* winCost)
+{
+    if (!c || !d_src || !n || !d_dst || !meta) return GC_ERR_PARAM;
+    const uint32_t nBlocks = gc_num_blocks(n);
+    const uint32_t fArg = lz_frame_arg(GC_CODEC_FLZMA2, level, nBlocks, c->dbgFrameBlocks);
+    const uint32_t frameBlocks = MF_F(fArg), groupBlocks = MF_C(fArg);
+    const uint32_t dp = gc_flzma2_dict_prop(level);
+    const uint64_t dictSize = (uint64_t)(2u | (dp & 1u)) << (dp / 2u + 11u);
+    size_t seqTotal = 0;
+    for (uint32_t b = 0; b < nBlocks; b++) {
+        const size_t base = (size_t)b * GC_ZSTD_BLOCK_MAX;
+        const uint32_t blockLen = (uint32_t)(n - base < GC_ZSTD_BLOCK_MAX ? n - base : GC_ZSTD_BLOCK_MAX);
+        const GcBlockMeta m = meta[b];
+        const char* bad = nullptr;
+        if (m.nSeqRaw > GC_MAX_SEQ_PER_BLOCK) bad = "more records than a block's workspace holds";
+        else if (m.nLit > blockLen) bad = "more literals than the block is long";
+        else if (m.nSeqRaw && !seq) bad = "records counted but not given";
+        // how far back a match of this block may reach: to the start of its frame (frames that tile the input) or of its group (overlapping frames: a frame's length
+        // at most), and never further than the dictionary size the coder properties state
+        const uint64_t frameStart = MF_S(fArg) == frameBlocks ? (uint64_t)(b / frameBlocks) * frameBlocks * GC_ZSTD_BLOCK_MAX : (uint64_t)(b / groupBlocks) * groupBlocks * GC_ZSTD_BLOCK_MAX;
+        uint64_t limit = (uint64_t)frameBlocks * GC_ZSTD_BLOCK_MAX; if (limit > dictSize) limit = dictSize;
+        uint64_t covered = m.nLit, matched = 0; uint32_t prevRank = 0;
+        for (uint32_t i = 0; !bad && i < m.nSeqRaw; i++) {
+            const GcSeqRaw r = seq[seqTotal + i];
+            const uint32_t ml = r.offml & 0xFFu, off = r.offml >> 8;
+            const uint64_t pos = base + r.litRank + matched;
+            if (r.litRank < prevRank || r.litRank > m.nLit) bad = "litRank decreases or exceeds nLit";
+            else if (ml == 0u) bad = "a record of length 0";
+            else if (off == 0u) bad = "an offset of 0";
+            else if (off > pos) bad = "an offset that reaches in front of the input";
+            else if (off > pos - frameStart || off > limit) bad = "an offset that reaches in front of its frame or beyond the level's dictionary";
+            prevRank = r.litRank; matched += ml; covered += ml;
+        }
+        if (!bad && covered != blockLen) bad = "literals and matches do not add up to the block's length";
+        if (bad) { snprintf(c->err, sizeof(c->err), "parsed block %u: %s", b, bad); return GC_ERR_PARAM; }
+        seqTotal += m.nSeqRaw;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    c->timed = false;
+    int rc = ensure_workspace(c, nBlocks);
+    if (rc != GC_OK) return rc;
+    const GcFlzma2Stage stage = flzma2_stage(level, nBlocks, groupBlocks);
+    if ((rc = flzma2_reserve(c, nBlocks, stage.segLog)) != GC_OK) return rc;
+    if (winCost) { const GcWsNeed rows[] = { { c->mfWinCost, (size_t)nBlocks * 128u, "window costs" } }; if ((rc = mf_reserve(c, rows, 1)) != GC_OK) return rc; }
+    if (c->profOn) { HIPCHK(c, hipMemsetAsync(c->prof, 0, (GC_LZ_PHASES + GC_SEQ_PHASES) * sizeof(unsigned long long), c->stream)); c->profBlocks = 1u; }
+    HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+    c->mfTimed = false; c->mfParts = 0; c->mfPriced = false; c->nParts = 1u;
+    HIPCHK(c, hipEventRecord(c->evPart[0][0], c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->meta, meta, (size_t)nBlocks * sizeof(GcBlockMeta), hipMemcpyHostToDevice, c->stream));
+    seqTotal = 0;
+    for (uint32_t b = 0; b < nBlocks; b++) {       // K1's stride
+        if (meta[b].nSeqRaw) HIPCHK(c, hipMemcpyAsync(c->seqRaw + (size_t)b * GC_MAX_SEQ_PER_BLOCK, seq + seqTotal, (size_t)meta[b].nSeqRaw * sizeof(GcSeqRaw), hipMemcpyHostToDevice, c->stream));
+        seqTotal += meta[b].nSeqRaw;
+    }
+    if (winCost) HIPCHK(c, hipMemcpyAsync(c->mfWinCost, winCost, (size_t)nBlocks * 128u, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                           // (the caller's buffers are pageable and his again when this returns)
+    HIPCHK(c, hipEventRecord(c->evPart[0][1], c->stream));
+    rc = flzma2_code_part(c, stage, 0, (const uint8_t*)d_src, n, 0, nBlocks, winCost ? (const uint32_t*)c->mfWinCost : nullptr);
+    if (rc != GC_OK) return rc;
+    return flzma2_join_and_emit(c, stage, (const uint8_t*)d_src, d_dst, dstCap, nBlocks, 1u, flags);
+}
+
+// Test entry (the test builds only): L3a and L3b (gc_lzma2_rc_kernel, gc_lzma2_rc_fin_kernel) on a caller's (probability, bit) words.  HOST memory throughout.  words: the
+// word stream as L2 leaves it, nWords = segments x GC_LZMA_STREAM_WORDS(segLog), segment s at s x that; chunks: nRc entries as L2 leaves them (usize 0 = absent, a group's
+// leader carries the usize of all its members and the members behind it are absent; csize 0xFFFFFFFF = not coded).  out: nRc x GC_LZMA_RC_STRIDE bytes, every chunk's staging
+// area; csize: nRc words, the coded bytes of every chunk (0xFFFFFFFF: it outgrew its staging area or an LZMA2 chunk).  Refused: an adaptive word whose probability is outside
+// 31..2017 -- what shift-5 adaptation keeps a probability in, and what rc_word's "one shift step suffices" rests on -- and a chunk whose words or members leave its segment.
+extern "C" int gc_test_lzma2_rc_words(gc_ctx* c, const uint16_t* words, size_t nWords, const GcLzmaChunkInfo* chunks, uint32_t nRc, uint32_t segLog, uint8_t* out, uint32_t* csize)
+{
+    if (!c || !words || !chunks || !nRc || !out || !csize) return GC_ERR_PARAM;
+    if (segLog < GC_LZMA_SEG_LOG_MIN || segLog > GC_LZMA_SEG_LOG_MAX) { snprintf(c->err, sizeof(c->err), "rc words: segLog outside %u..%u", GC_LZMA_SEG_LOG_MIN, GC_LZMA_SEG_LOG_MAX); return GC_ERR_PARAM; }
+    const uint32_t rcPerSeg = 1u << (segLog - GC_LZMA_RC_LOG), place = GC_LZMA_STREAM_WORDS(segLog);
+    const uint32_t nBlocks = (nRc + GC_LZMA_RC_PER_BLOCK - 1u) / GC_LZMA_RC_PER_BLOCK, nSegs = nBlocks * (GC_ZSTD_BLOCK_MAX >> segLog);
+    if (nWords != (size_t)nSegs * place) { snprintf(c->err, sizeof(c->err), "rc words: %zu words do not cover the places of %u segments (%u each)", nWords, nSegs, place); return GC_ERR_PARAM; }
+    uint32_t prevEnd = 0;
+    for (uint32_t k = 0; k < nRc; k++) {
+        const GcLzmaChunkInfo ci = chunks[k];
+        if ((k & (rcPerSeg - 1u)) == 0u) prevEnd = 0;
+        if (ci.usize == 0u || ci.csize == 0xFFFFFFFFu) continue;
+        const uint16_t* W = words + (size_t)(k / rcPerSeg) * place;
+        const uint32_t members = (ci.usize + GC_LZMA_RC_SIZE - 1u) >> GC_LZMA_RC_LOG;
+        const char* bad = nullptr;
+        if (ci.wordStart > ci.wordEnd || ci.wordEnd > place || ci.wordStart < prevEnd) bad = "its word range leaves its segment's place or overlaps the chunk in front";
+        else if (members > GC_LZMA_RC_GROUP_MAX || (k & (rcPerSeg - 1u)) + members > rcPerSeg || k + members > nRc) bad = "its members leave its segment";
+        for (uint32_t j = 1; !bad && j < members; j++) if (chunks[k + j].usize != 0u) bad = "a member behind the leader is not absent";
+        for (uint32_t w = ci.wordStart; !bad && w < ci.wordEnd; w++) {
+            const uint32_t v = W[w];
+            if ((v & 0x4000u) == 0u && ((v & 0x7FFu) < 31u || (v & 0x7FFu) > 2017u)) bad = "an adaptive word with a probability outside 31..2017";
+        }
+        if (bad) { snprintf(c->err, sizeof(c->err), "rc words, chunk %u: %s", k, bad); return GC_ERR_PARAM; }
+        prevEnd = ci.wordEnd;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    c->timed = false;
+    int rc = ensure_workspace(c, nBlocks);
+    if (rc != GC_OK) return rc;
+    if ((rc = flzma2_reserve(c, nBlocks, segLog)) != GC_OK) return rc;
+    HIPCHK(c, hipMemsetAsync(c->lzInfo, 0, (size_t)nBlocks * GC_LZMA_RC_PER_BLOCK * sizeof(GcLzmaChunkInfo), c->stream));      // (chunks behind nRc: absent)
+    HIPCHK(c, hipMemcpyAsync(c->lzInfo, chunks, (size_t)nRc * sizeof(GcLzmaChunkInfo), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->lzStream, words, nWords * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->lzRcOut, 0, (size_t)nRc * GC_LZMA_RC_STRIDE, c->stream));
+    rc = flzma2_range_code(c, c->stream, segLog, 0, nRc);
+    if (rc != GC_OK) return rc;
+    HIPCHK(c, hipMemcpyAsync(out, c->lzRcOut, (size_t)nRc * GC_LZMA_RC_STRIDE, hipMemcpyDeviceToHost, c->stream));
+    std::vector<GcLzmaChunkInfo> got(nRc);
+    HIPCHK(c, hipMemcpyAsync(got.data(), c->lzInfo, (size_t)nRc * sizeof(GcLzmaChunkInfo), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    c->pending = true; c->timed = true; c->lastCodec = 1;
+    for (uint32_t k = 0; k < nRc; k++) csize[k] = got[k].csize;
     return GC_OK;
 }
+#endif
 
 extern "C" int gc_flzma2_finish(gc_ctx* c, size_t* compressedSize) { return gc_zstd_finish(c, compressedSize); }
 

@@ -674,7 +674,8 @@ gc_lzma2_model_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, const u
             cLits = gc_readlane(aIncl, lastLane) - gc_readlane(aIncl, ml_);
         } else cLits += gc_readlane(aIncl, lastLane);
         cMatch = mLast;
-        if (rep4) {
+        {   // (with the hook GC_L2_REP4=0 as well: the list's front decides in the NEXT tile whether a one-byte item is a short repeat, and without rep2 / rep3 coding
+            //  the front is still the last distance used.  Carried only under rep4, a one-byte item of a later tile was held against the list of the segment's start.)
             LzLru t; t.v0 = gc_readlane(lruIncl.v0, lastLane); t.v1 = gc_readlane(lruIncl.v1, lastLane); t.v2 = gc_readlane(lruIncl.v2, lastLane); t.v3 = gc_readlane(lruIncl.v3, lastLane);
             cLru = lru_over(t, cLru);
         }
