@@ -582,6 +582,29 @@ class BrotliEncoder(_EncoderBase):
         self._check(self._lib.gc_brotli_last_timing(self._ctx, ms), "gc_brotli_last_timing")
         return dict(zip(self.KERNELS, [float(x) for x in ms]))
 
+    PLAIN, NOT_FIRST, NOT_LAST = 1, 2, 4
+
+    def code_parsed_device(self, d_src_ptr, n, d_dst_ptr, dst_cap, blocks, plain=0, rep_sub=0, ctx_model=False):
+        """TEST BUILDS ONLY (csrc/libgpucodec_hooks.so, the emulator library): the stream call with the match finder replaced by a stated parse (gc_api.hip
+        gc_test_brotli_encode_parsed).  blocks: per 128 KiB block of the n bytes at d_src_ptr a pair (literals, records) -- the block's literal bytes in order (the
+        trailing ones included) and a (k, 2) uint32 array of K1's records, [literals in front of the copy, offset << 8 | copy length (2..255)]; a copy longer than 255
+        is a chain of records of one offset with no literals between them (tests/brotli_parse.py derives them).  self.level gives the blocks per brotli-mt chunk;
+        plain: 0, or PLAIN [| NOT_FIRST] [| NOT_LAST] for a piece of one plain stream; rep_sub: passes of the last-distance substitution; ctx_model: thirteen literal
+        trees may be chosen.  The library refuses a parse that does not tile its block or reaches in front of its chunk; finish() reads the size as usual."""
+        import numpy as np
+        fn = getattr(self._lib, "gc_test_brotli_encode_parsed", None)
+        if fn is None:
+            raise GpuCodecError("gc_test_brotli_encode_parsed: this library is not a test build")
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
+        fn.restype = C.c_int
+        lits = [np.ascontiguousarray(l, dtype=np.uint8).ravel() for l, _ in blocks]
+        recs = [np.ascontiguousarray(r, dtype=np.uint32).reshape(-1, 2) for _, r in blocks]
+        meta = np.array([[r.shape[0], l.size] for l, r in zip(lits, recs)], dtype=np.uint32).reshape(-1, 2)
+        lit = np.concatenate(lits + [np.zeros(1, np.uint8)])
+        rec = np.ascontiguousarray(np.concatenate(recs + [np.zeros((1, 2), np.uint32)]))
+        self._check(fn(self._ctx, d_src_ptr, n, d_dst_ptr, dst_cap, self.level, int(plain), int(rep_sub), 1 if ctx_model else 0, lit.ctypes.data, rec.ctypes.data, meta.ctypes.data),
+                    "gc_test_brotli_encode_parsed")
+
 
 class BrotliDecoder(_EncoderBase):
     """Mirror of NCompress::NBROTLI::CDecoder (CPP/7zip/Compress/BrotliDecoder.cpp:124) for whole brotli-mt streams: one wave per chunk on the GPU.  A stream that refers to

@@ -1469,6 +1469,26 @@ extern "C" size_t gc_brotli_compress_bound(size_t n)
     return n + nb * 8u + (nb / 8u + 1u) * 17u + 32u;
 }
 
+// What follows the finder in the brotli stream call -- B1, plan, emit on the literals, records and block metas that are in the workspace -- shared with the test entry
+// gc_test_brotli_encode_parsed (below), so that what the tests feed an exact parse runs the product's launches and nothing else.  ev[0] is recorded by the caller.
+// The stage is cleared here (B1 ORs its bits into it), in front of ev[1]: the clearing counts with the finder's phase, B1's time is B1's alone.
+static int brotli_code_blocks(gc_ctx* c, const uint8_t* src, size_t n, void* d_dst, size_t dstCap, uint32_t nBlocks, uint32_t bpc, uint32_t plainFlags, uint32_t repSub, uint32_t ctxModel)
+{
+    HIPCHK(c, hipMemsetAsync(c->brStage, 0, (size_t)nBlocks * GC_BR_STAGE_STRIDE, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+    GC_LAUNCH(gc_brotli_block_kernel, nBlocks, 256, c->stream, src, (uint64_t)n, (const GcSeqRaw*)c->seqRaw, (const uint8_t*)c->lit,
+              (const GcBlockMeta*)c->meta, c->seqPacked, c->seqOff, bpc, plainFlags, repSub, ctxModel, (uint32_t*)c->brStage.p, c->brInfo);
+    HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+    GC_LAUNCH(gc_brotli_plan_kernel, 1, 1024, c->stream, (const GcBrotliBlockInfo*)c->brInfo, nBlocks, bpc, (uint64_t)dstCap, c->brPlan, c->result);
+    HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+    GC_LAUNCH(gc_brotli_emit_kernel, nBlocks, 256, c->stream, src, (uint64_t)n, (const uint8_t*)c->brStage, (const GcBrotliBlockInfo*)c->brInfo,
+              (const GcBrotliPlan*)c->brPlan, nBlocks, bpc, plainFlags, (const uint64_t*)c->result, (uint8_t*)d_dst);
+    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+    HIPCHK(c, hipGetLastError());
+    c->pending = true; c->timed = true; c->lastCodec = 2;
+    return GC_OK;
+}
+
 extern "C" int gc_brotli_compress_device(gc_ctx* c, const void* d_src, size_t n, void* d_dst, size_t dstCap, int level)
 {
     if (!c || (!d_src && n) || !d_dst) return GC_ERR_PARAM;
@@ -1490,30 +1510,74 @@ extern "C" int gc_brotli_compress_device(gc_ctx* c, const void* d_src, size_t n,
     if (rc != GC_OK) return rc;
     const uint32_t bpc = c->optBrotliPlain ? 0xFFFFFFFFu : brotli_blocks_per_chunk(level);     // plain: one stream (B1 writes the stream header once, B2 / B3 no frame headers)
     const uint8_t* src = (const uint8_t*)d_src;
-    HIPCHK(c, hipMemsetAsync(c->brStage, 0, (size_t)nBlocks * GC_BR_STAGE_STRIDE, c->stream));
     const GcLzPlan plan = with_hooks(brotli_plan(level));
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
     rc = launch_finder(c, plan, src, n, lz_frame_arg(GC_CODEC_BROTLI, level, nBlocks, 0u), nullptr);
     if (rc != GC_OK) return rc;
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     uint32_t brRepSub = 2u;                                    // B1's last-distance substitution (gc_brotli.hip): two passes.  Emulator, quality 6, x the reference, passes 0 / 1 / 2 / 3 / 4: shared objects
                                                                // 8 MiB 1.1262 / 1.1095 / 1.0969 / 1.0919 / 1.0888 (2 MiB: 1.0925 / 1.0788 / 1.0771), sources 8 MiB 1.1594 / 1.1439 / 1.1392; a pass carries a
                                                                // distance three commands further along a run of records and costs 0.86 ms per 500 MB on the device (B1 5.4 ms without)
     gc_env_u32("GC_BR_REPSUB", 0u, 64u, &brRepSub);                                             // test hook
     uint32_t brCtx = level >= 5 ? 1u : 0u;                     // literal context modelling from quality 5 (the reference: MIN_QUALITY_FOR_CONTEXT_MODELING, C/brotli/enc/quality.h): B1 chooses one tree or thirteen per meta-block
     gc_env_u32("GC_BR_CTX", 0u, 1u, &brCtx);                                                    // test hook
-    GC_LAUNCH(gc_brotli_block_kernel, nBlocks, 256, c->stream, src, (uint64_t)n, (const GcSeqRaw*)c->seqRaw, (const uint8_t*)c->lit,
-              (const GcBlockMeta*)c->meta, c->seqPacked, c->seqOff, bpc, c->optBrotliPlain, brRepSub, brCtx, (uint32_t*)c->brStage.p, c->brInfo);
-    HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-    GC_LAUNCH(gc_brotli_plan_kernel, 1, 1024, c->stream, (const GcBrotliBlockInfo*)c->brInfo, nBlocks, bpc, (uint64_t)dstCap, c->brPlan, c->result);
-    HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-    GC_LAUNCH(gc_brotli_emit_kernel, nBlocks, 256, c->stream, src, (uint64_t)n, (const uint8_t*)c->brStage, (const GcBrotliBlockInfo*)c->brInfo,
-              (const GcBrotliPlan*)c->brPlan, nBlocks, bpc, c->optBrotliPlain, (const uint64_t*)c->result, (uint8_t*)d_dst);
-    HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-    HIPCHK(c, hipGetLastError());
-    c->pending = true; c->timed = true; c->lastCodec = 2;
-    return GC_OK;
+    return brotli_code_blocks(c, src, n, d_dst, dstCap, nBlocks, bpc, c->optBrotliPlain, brRepSub, brCtx);
 }
+
+#ifdef GC_TEST_HOOKS
+// Test entry (the test builds only; not part of include/gpucodec.h): the brotli stream call with the match finder replaced by a parse the caller states, so that a test
+// decides exactly which commands B1 gets.  d_src / d_dst: device memory, as in gc_brotli_compress_device.  lit / seq / meta: HOST memory, what K1 leaves per block
+// (gc_common.h), packed -- block b's literals follow block b - 1's, its records likewise, meta[b] counts both.  level: the blocks per brotli-mt chunk; plainFlags: 0 = brotli-mt
+// frames, otherwise bit 0 = one plain stream, bit 1 = not its first piece, bit 2 = not its last (the context option's values); repSub: passes of the last-distance
+// substitution; ctxModel: literal context modelling allowed.  None of them is read from the environment.  The parse is checked here, on the host, before anything is
+// launched.  (That it REPRODUCES the input is the caller's business.)  gc_brotli_finish reads the result.
+extern "C" int gc_test_brotli_encode_parsed(gc_ctx* c, const void* d_src, size_t n, void* d_dst, size_t dstCap, int level, unsigned plainFlags, unsigned repSub, unsigned ctxModel,
+                                            const uint8_t* lit, const GcSeqRaw* seq, const GcBlockMeta* meta)
+{
+    if (!c || !d_src || !n || !d_dst || !meta || plainFlags > 7u || (plainFlags != 0u && !(plainFlags & 1u)) || repSub > 64u || ctxModel > 1u) return GC_ERR_PARAM;
+    const uint32_t nBlocks = gc_num_blocks(n);
+    const uint32_t bpc = plainFlags ? 0xFFFFFFFFu : brotli_blocks_per_chunk(level);
+    size_t litTotal = 0, seqTotal = 0;
+    for (uint32_t b = 0; b < nBlocks; b++) {
+        const size_t base = (size_t)b * GC_ZSTD_BLOCK_MAX;
+        const uint32_t blockLen = (uint32_t)(n - base < GC_ZSTD_BLOCK_MAX ? n - base : GC_ZSTD_BLOCK_MAX);
+        const GcBlockMeta m = meta[b];
+        const char* bad = nullptr;
+        if (m.nSeqRaw > GC_MAX_SEQ_PER_BLOCK) bad = "more records than a row of the workspace holds";
+        else if (m.nLit > blockLen) bad = "more literals than the block is long";
+        else if ((m.nLit && !lit) || (m.nSeqRaw && !seq)) bad = "counts without data";
+        // how far back a copy may reach: to the first byte of the block's brotli-mt chunk; in a plain stream to the first byte of this call
+        const uint64_t inChunk = plainFlags ? (uint64_t)base : (uint64_t)(b % bpc) * GC_ZSTD_BLOCK_MAX;
+        uint64_t covered = m.nLit, matched = 0; uint32_t prevRank = 0;
+        for (uint32_t i = 0; !bad && i < m.nSeqRaw; i++) {
+            const GcSeqRaw r = seq[seqTotal + i];
+            const uint32_t ml = r.offml & 0xFFu, off = r.offml >> 8;
+            if (r.litRank < prevRank || r.litRank > m.nLit) bad = "litRank decreases or exceeds nLit";
+            else if (ml < 2u) bad = "a copy shorter than 2";
+            else if (off == 0u) bad = "an offset of 0";
+            else if (off > inChunk + r.litRank + matched) bad = "an offset that reaches in front of the chunk";
+            prevRank = r.litRank; matched += ml; covered += ml;
+        }
+        if (!bad && covered != blockLen) bad = "literals and copies do not add up to the block's length";
+        if (bad) { snprintf(c->err, sizeof(c->err), "parsed block %u: %s", b, bad); return GC_ERR_PARAM; }
+        litTotal += m.nLit; seqTotal += m.nSeqRaw;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    c->timed = false;
+    int rc = ensure_workspace(c, nBlocks);
+    if (rc != GC_OK) return rc;
+    HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+    c->mfTimed = false; c->mfParts = 0; c->mfPriced = false;
+    HIPCHK(c, hipMemcpyAsync(c->meta, meta, (size_t)nBlocks * sizeof(GcBlockMeta), hipMemcpyHostToDevice, c->stream));
+    litTotal = 0; seqTotal = 0;
+    for (uint32_t b = 0; b < nBlocks; b++) {       // K1's strides
+        if (meta[b].nLit) HIPCHK(c, hipMemcpyAsync(c->lit + (size_t)b * GC_ZSTD_BLOCK_MAX, lit + litTotal, meta[b].nLit, hipMemcpyHostToDevice, c->stream));
+        if (meta[b].nSeqRaw) HIPCHK(c, hipMemcpyAsync(c->seqRaw + (size_t)b * GC_MAX_SEQ_PER_BLOCK, seq + seqTotal, (size_t)meta[b].nSeqRaw * sizeof(GcSeqRaw), hipMemcpyHostToDevice, c->stream));
+        litTotal += meta[b].nLit; seqTotal += meta[b].nSeqRaw;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));                           // (the caller's buffers are pageable and his again when this returns)
+    return brotli_code_blocks(c, (const uint8_t*)d_src, n, d_dst, dstCap, nBlocks, bpc, plainFlags, repSub, ctxModel);
+}
+#endif
 
 extern "C" int gc_brotli_finish(gc_ctx* c, size_t* compressedSize) { return gc_zstd_finish(c, compressedSize); }
 

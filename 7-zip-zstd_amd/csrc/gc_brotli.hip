@@ -461,8 +461,12 @@ gc_brotli_block_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, const 
     // trailing literals form an insert-only command
     const uint32_t litBeforeTail = nRaw ? R[nRaw - 1u].litRank : 0u;
     const uint32_t tailLen = nLit - litBeforeTail;
-    const uint32_t nCmd = nSeq + (tailLen ? 1u : 0u);
-    if (t == 0 && tailLen) { P[nSeq] = (uint64_t)tailLen; LS[nSeq] = litBeforeTail; }
+    // A row of P / LS holds GC_MAX_SEQ_PER_BLOCK entries: with that many commands AND literals behind the last record there is no entry left for the tail (P[nSeq] would be
+    // the next block's row, or lie behind the buffer).  Such a block is stored and has no commands at all; no finder gets there (W6 and W6r share 26208..26220 entries out)
+    const bool rowFull = tailLen != 0u && nSeq >= GC_MAX_SEQ_PER_BLOCK;    // uniform
+    const uint32_t nCmd = rowFull ? 0u : nSeq + (tailLen ? 1u : 0u);
+    if (rowFull) nSeq = 0u;
+    if (t == 0 && tailLen && !rowFull) { P[nSeq] = (uint64_t)tailLen; LS[nSeq] = litBeforeTail; }
     __syncthreads();
 
     // ---- last-distance substitution (round 4; repSub passes): a copy of up to BR_SUB_MAX bytes whose bytes ALSO match at the previous command's distance
@@ -628,7 +632,7 @@ gc_brotli_block_kernel(const uint8_t* __restrict__ src, uint64_t srcSize, const 
     __syncthreads();
 
     // ---- prefix codes
-    bool ok = true;
+    bool ok = !rowFull;
     for (uint32_t tr = 0; tr < nTrees; tr++) {
         const uint32_t ns = br_build_code(hLit[tr], 256u, 15u, dLit[tr], cLit[tr], S, &ok);
         if (t == 0) { uint32_t one = 0; if (ns == 1u) { for (uint32_t s = 0; s < 256u; s++) if (hLit[tr][s]) one = s; } sNs[tr] = ns; sOne[tr] = one; }

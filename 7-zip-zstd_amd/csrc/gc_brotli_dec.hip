@@ -609,6 +609,7 @@ __device__ __forceinline__ void brd_kernel_body(const uint8_t* __restrict__ src,
                 const uint8_t* s = src + ck.srcOff + gc_uniform(sMeta.srcAt);
                 gc_wave_sync();
                 brd_flush<RING>(sRing, out, flushed, pos, lane);
+                gc_wave_sync();                                       // (every lane's part of the flush has read the ring before a stored block of the ring's size or more overwrites all of it)
                 for (uint32_t i = lane; i < mlen; i += 64u) { const uint8_t v = s[i]; out[pos + i] = v; sRing[(pos + i) & RMASK] = v; }
                 p2 = mlen > 1u ? gc_uniform(s[mlen - 2u]) : p1; p1 = gc_uniform(s[mlen - 1u]);
                 pos += mlen; flushed = pos;
