@@ -9,7 +9,6 @@
 #include "gc_lzma2.h"
 #include "gc_brotli.h"
 #include "gc_mf.h"
-#include "gc_zstd_dec.h"
 #ifdef HIPEMU
 #include "hip_runtime_stub.h"
 #else
@@ -22,6 +21,7 @@
 #include <new>
 #include "gc_host_stream.h"
 #include "gc_devbuf.h"
+#include "gc_zstd_dec.h"
 #include "gc_brotli_dec.h"
 #include "gc_lzma2_dec_work.h"
 #ifdef GC_TEST_HOOKS
@@ -29,93 +29,10 @@
 #include <unistd.h>
 #endif
 
-struct GcFramePlan { uint64_t off; uint32_t size; uint32_t compressed; };
-
 // FLZMA2 can process its input in up to GC_MAX_PARTS frame-aligned parts whose stages (match finder, model, range coder) run on
 // different HIP streams, stage k of part p overlapping stage k-1 of part p+1.  Off by default: see gc_flzma2_compress_device.
 #define GC_MAX_PARTS   8u
 #define GC_PART_EVENTS 8u    // 0 finder start, 1 finder end (= prep start), 2 prep end, 3 model start, 4 model end, 5 rc start, 6 rc end
-
-extern "C" __global__ void gc_zstd_lz_kernel(const uint8_t*, uint64_t, GcSeqRaw*, uint8_t*, GcBlockMeta*, unsigned long long*);
-extern "C" __global__ void gc_zstd_huf_kernel(const uint8_t*, const GcBlockMeta*, uint8_t*, GcSectionInfo*);
-extern "C" __global__ void gc_zstd_seq_codes_kernel(const GcSeqRaw*, const GcBlockMeta*, uint64_t*, uint32_t*, uint8_t*, GcSeqHist*, uint8_t*, GcSectionInfo*, uint32_t, unsigned long long*);
-extern "C" __global__ void gc_zstd_seq_tables_kernel(const GcSeqHist*, const GcSectionInfo*, GcSeqTabG*, unsigned long long*);
-extern "C" __global__ void gc_zstd_seq_chain_kernel(const uint8_t*, const GcSectionInfo*, GcSeqTabG*, uint16_t*, unsigned long long*);
-extern "C" __global__ void gc_zstd_seq_pack_kernel(const uint64_t*, const uint8_t*, const uint16_t*, const GcSeqTabG*, uint8_t*, GcSectionInfo*, uint64_t, unsigned long long*);
-extern "C" __global__ void gc_wave_scan_test_kernel(const uint32_t*, const uint64_t*, uint32_t*, uint32_t*, uint64_t*);      // (gc_zstd_seq.hip; launched by gc_test_wave_scans only)
-extern "C" __global__ void gc_zstd_plan_kernel(const GcSectionInfo*, uint32_t, uint64_t, uint64_t, uint32_t, GcFramePlan*, uint64_t*, uint32_t, uint32_t);
-extern "C" __global__ void gc_zstd_emit_kernel(const uint8_t*, uint64_t, const uint8_t*, const uint8_t*, const GcSectionInfo*,
-                                               const GcFramePlan*, const uint64_t*, uint32_t, uint32_t, uint8_t*, const uint64_t*);
-extern "C" __global__ void gc_zstd_xxh64_kernel(const uint8_t*, uint64_t, uint64_t, uint32_t, uint64_t, uint64_t*);      // K0x (gc_xxh64.h)
-// the batch forms of K1, K3d, K4, K5 and K0x: an item table where the others derive a block's place and length from the stream's size (gc_zstd_batch.h)
-extern "C" __global__ void gc_zstd_lz_batch_kernel(const uint8_t*, const gc_batch_item*, GcSeqRaw*, uint8_t*, GcBlockMeta*);
-extern "C" __global__ void gc_zstd_lz_batch_dict_kernel(const uint8_t*, const gc_batch_item*, GcSeqRaw*, uint8_t*, GcBlockMeta*, const uint8_t*, uint32_t, const uint32_t*, const uint32_t*);
-extern "C" __global__ void gc_zstd_dict_digest_kernel(const uint8_t*, uint32_t, uint32_t*, uint32_t*);
-extern "C" __global__ void gc_zstd_seq_pack_batch_kernel(const uint64_t*, const uint8_t*, const uint16_t*, const GcSeqTabG*, uint8_t*, GcSectionInfo*, const gc_batch_item*);
-extern "C" __global__ void gc_zstd_plan_batch_kernel(const GcSectionInfo*, const gc_batch_item*, uint32_t, uint64_t, GcFramePlan*, gc_batch_result*, uint64_t*, uint32_t);
-extern "C" __global__ void gc_zstd_emit_batch_kernel(const uint8_t*, const gc_batch_item*, const uint8_t*, const uint8_t*, const GcSectionInfo*, const GcFramePlan*, const uint64_t*,
-                                                     uint8_t*, const uint64_t*);
-extern "C" __global__ void gc_zstd_xxh64_batch_kernel(const uint8_t*, const gc_batch_item*, uint64_t*);
-
-extern "C" __global__ void gc_mf_count_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t*);
-extern "C" __global__ void gc_mf_scan_kernel(uint32_t*, uint32_t);
-extern "C" __global__ void gc_mf_scatter_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, GcMfEntry*);
-extern "C" __global__ void gc_mf_link_kernel(const uint32_t*, const GcMfEntry*, GcMfEntry*, uint32_t, uint64_t, uint32_t, uint32_t*);
-extern "C" __global__ void gc_mf_verify_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, const GcMfEntry*, uint32_t*);
-extern "C" __global__ void gc_mf_count_short_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t*);
-extern "C" __global__ void gc_mf_scatter_short_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, GcMfEntry*);
-extern "C" __global__ void gc_mf_verify_short_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, const GcMfEntry*, const uint32_t*, uint32_t*, const uint32_t*);
-extern "C" __global__ void gc_mf_verify_shortb_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, const GcMfEntry*, const uint32_t*, uint32_t*, const uint32_t*);
-extern "C" __global__ void gc_mf_count_far_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t*);
-extern "C" __global__ void gc_mf_scatter_far_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, GcMfEntry*);
-extern "C" __global__ void gc_mf_verify_far_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, const GcMfEntry*, uint32_t*);
-extern "C" __global__ void gc_mf_count_far2_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t*);
-extern "C" __global__ void gc_mf_scatter_far2_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, GcMfEntry*);
-extern "C" __global__ void gc_mf_verify_far2_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, const GcMfEntry*, uint32_t*);
-extern "C" __global__ void gc_mf_deepen_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t*, uint32_t*, uint32_t*);
-extern "C" __global__ void gc_mf_count_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t*);
-extern "C" __global__ void gc_mf_scan_kernel_p8(uint32_t*, uint32_t);
-extern "C" __global__ void gc_mf_scatter_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, GcMfEntry*);
-extern "C" __global__ void gc_mf_link_kernel_p8(const uint32_t*, const GcMfEntry*, GcMfEntry*, uint32_t, uint64_t, uint32_t, uint32_t*);
-extern "C" __global__ void gc_mf_verify_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, const GcMfEntry*, uint32_t*);
-extern "C" __global__ void gc_mf_count_short_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t*);
-extern "C" __global__ void gc_mf_scatter_short_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, GcMfEntry*);
-extern "C" __global__ void gc_mf_verify_short_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, const GcMfEntry*, const uint32_t*, uint32_t*, const uint32_t*);
-extern "C" __global__ void gc_mf_verify_shortb_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, const GcMfEntry*, const uint32_t*, uint32_t*, const uint32_t*);
-extern "C" __global__ void gc_mf_count_far_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t*);
-extern "C" __global__ void gc_mf_scatter_far_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, GcMfEntry*);
-extern "C" __global__ void gc_mf_verify_far_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, const GcMfEntry*, uint32_t*);
-extern "C" __global__ void gc_mf_count_far2_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t*);
-extern "C" __global__ void gc_mf_scatter_far2_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, GcMfEntry*);
-extern "C" __global__ void gc_mf_verify_far2_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, const GcMfEntry*, uint32_t*);
-extern "C" __global__ void gc_mf_deepen_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t*, uint32_t*, uint32_t*);
-extern "C" __global__ void gc_mf_vparse_tile_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t*, const GcMfEntry*, GcSeqRaw*, uint8_t*, GcBlockMeta*, uint32_t*, uint32_t*, unsigned long long*);
-extern "C" __global__ void gc_mf_vparse_tile_kernel_p8(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t*, const GcMfEntry*, GcSeqRaw*, uint8_t*, GcBlockMeta*, uint32_t*, uint32_t*, unsigned long long*);
-extern "C" __global__ void gc_mf_ringparse_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t*, GcSeqRaw*, uint8_t*, GcBlockMeta*);
-extern "C" __global__ void gc_mf_parse_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, GcSeqRaw*, uint8_t*, GcBlockMeta*, uint16_t*, uint32_t);
-extern "C" __global__ void gc_mf_short_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint16_t*);
-extern "C" __global__ void gc_mf_dp2_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t, const uint32_t*, const uint16_t*, const uint16_t*, uint32_t*, uint32_t*);
-extern "C" __global__ void gc_mf_dp3_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t, const uint32_t*, const uint16_t*, const uint16_t*, uint32_t*, uint32_t*);
-extern "C" __global__ void gc_mf_litprice_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, const uint16_t*, uint32_t, uint8_t*);
-extern "C" __global__ void gc_mf_dpl2_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t, const uint32_t*, const uint16_t*, const uint16_t*, uint32_t*, uint32_t*, const uint8_t*);
-extern "C" __global__ void gc_mf_dpl2s_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t, const uint32_t*, const uint16_t*, const uint16_t*, uint32_t*, uint32_t*, const uint8_t*);
-extern "C" __global__ void gc_mf_dplz_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t, const uint32_t*, const uint16_t*, const uint16_t*, uint32_t*, uint32_t*, const uint8_t*);
-extern "C" __global__ void gc_mf_dplzs_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t, const uint32_t*, const uint16_t*, const uint16_t*, uint32_t*, uint32_t*, const uint8_t*);
-
-extern "C" __global__ void gc_lzma2_prep_kernel(const GcSeqRaw*, const GcBlockMeta*, uint64_t, uint64_t*, uint32_t*);
-extern "C" __global__ void gc_lzma2_model_kernel(const uint8_t*, uint64_t, const uint64_t*, const uint32_t*, uint32_t, uint32_t, uint16_t*, GcLzmaChunkInfo*, const uint32_t*, unsigned long long*, uint32_t, uint32_t, uint32_t, uint8_t*, uint32_t, uint32_t, uint32_t);
-extern "C" __global__ void gc_lzma2_segkind_kernel(const GcLzmaChunkInfo*, const uint8_t*, uint32_t, uint32_t, uint8_t*);
-extern "C" __global__ void gc_lzma2_rc_kernel(uint16_t*, uint32_t, uint32_t, uint8_t*, GcLzmaChunkInfo*);
-extern "C" __global__ void gc_lzma2_rc_fin_kernel(const uint16_t*, uint32_t, uint32_t, uint8_t*, GcLzmaChunkInfo*);
-extern "C" __global__ void gc_lzma2_plan_kernel(const GcLzmaChunkInfo*, uint32_t, uint32_t, uint64_t, uint32_t, GcLzmaPlan*, uint64_t*, const uint8_t*, const uint8_t*);
-extern "C" __global__ void gc_lzma2_emit_kernel(const uint8_t*, uint32_t, const uint8_t*, const GcLzmaChunkInfo*, const GcLzmaPlan*, uint32_t,
-                                                uint32_t, const uint64_t*, uint8_t*, const uint8_t*);
-
-extern "C" __global__ void gc_brotli_block_kernel(const uint8_t*, uint64_t, const GcSeqRaw*, const uint8_t*, const GcBlockMeta*, uint64_t*, uint32_t*,
-                                                  uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*, GcBrotliBlockInfo*);
-extern "C" __global__ void gc_brotli_plan_kernel(const GcBrotliBlockInfo*, uint32_t, uint32_t, uint64_t, GcBrotliPlan*, uint64_t*);
-extern "C" __global__ void gc_brotli_emit_kernel(const uint8_t*, uint64_t, const uint8_t*, const GcBrotliBlockInfo*, const GcBrotliPlan*, uint32_t,
-                                                 uint32_t, uint32_t, const uint64_t*, uint8_t*);
 
 struct gc_ctx {
     __attribute__((visibility("hidden"))) gc_ctx() = default;      // (hidden: the library exports its C functions, not these two)
@@ -224,11 +141,6 @@ extern "C" size_t gc_zstd_compress_bound(size_t n)
          + nb * 8;                                              // (+ the optional content checksums: 4 bytes behind every frame and 4 more per seek-table entry, every block a frame of its own at worst)
 }
 
-void gc_brd_release(GcBrDecWork* w);
-int gc_brd_decode(hipStream_t st, GcBrDecWork* w, const uint8_t* d_src, const gc_brotli_chunk* chunks, size_t nChunks, uint8_t* d_dst, size_t dstCap, size_t* produced, char* err, size_t errCap);
-void gc_l2d_release(GcL2dWork* w);
-int gc_l2d_decode(hipStream_t st, GcL2dWork* w, const uint8_t* d_src, size_t n, const gc_lzma2_unit* units, size_t nUnits, uint8_t* d_dst, size_t dstCap, unsigned dictProp,
-                  size_t* produced, char* err, size_t errCap);
 static void ctx_release(gc_ctx* c);
 static void batch_release(gc_ctx* c);      // (gc_zstd_batch.h)
 
@@ -568,6 +480,38 @@ static int ensure_finder_workspace(gc_ctx* c, const GcLzPlan& plan, size_t n, ui
     return mf_reserve(c, rows, sizeof(rows) / sizeof(rows[0]));
 }
 
+// The 17 kernels that exist once per geometry, as the launches below name them: count, scatter and verify by pass (gc_mf.h MF_BASE ..), the others once.  The list that
+// declares the kernels (gc_mf.h GC_MF_GEOM_KERNELS) fills both tables; a function binds `K` to the table of its geometry once.
+struct GcMfKernels {
+    decltype(&gc_mf_count_kernel) count[MF_PASSES]; decltype(&gc_mf_scatter_kernel) scatter[MF_PASSES];
+    decltype(&gc_mf_verify_kernel) verify[MF_PASSES];                          // (base, far, far2; the short pass takes the records so far as well:)
+    decltype(&gc_mf_verify_short_kernel) verifyShort, verifyShortB;            // (B: with the catch-up, gc_lz_window.hip)
+    decltype(&gc_mf_scan_kernel) scan; decltype(&gc_mf_link_kernel) link; decltype(&gc_mf_deepen_kernel) deepen; decltype(&gc_mf_vparse_tile_kernel) vparseTile;
+};
+#define MF_BIND(slot, kernel, params) k.slot = kernel;
+static const GcMfKernels kWide = [] { GcMfKernels k = {}; GC_MF_GEOM_KERNELS(MF_BIND, ) return k; }();
+static const GcMfKernels kFast = [] { GcMfKernels k = {}; GC_MF_GEOM_KERNELS(MF_BIND, _p8) return k; }();
+#undef MF_BIND
+
+// W1..W4 of one pass over the frames of geometry g (frameArg: what made g): count -> scan -> scatter -> link.  Every pass of a part goes through the same count table and
+// entry lists.  W4 is a persistent launch: one-wave workgroups, six per CU (24 KiB of LDS each), fed from the ticket counter `ticket` (one counter per launch and part).
+// ev: four events, recorded behind W1, W2, W3 and W4 (the base pass), or null.
+static int mf_list_pass(gc_ctx* c, const GcMfKernels& K, hipStream_t st, int pass, const GcMfGeom& g, uint32_t frameArg, const uint8_t* src, size_t n,
+                        uint32_t* cnt, GcMfEntry* ent, GcMfEntry* ent2, uint32_t* ticket, hipEvent_t* ev)
+{
+    const uint32_t perT = gc_xcd_per(g.nTiles), nParts = 1u << g.partLog, linkWpc = 6u;
+    const uint32_t nLists = g.nFrames * nParts, linkGrid = nLists * GC_MF_LINK_SEGS < c->nCU * linkWpc ? nLists * GC_MF_LINK_SEGS : c->nCU * linkWpc;
+    GC_LAUNCH(K.count[pass], perT * GC_XCDS, nParts, st, src, (uint64_t)n, frameArg, g.nTiles, perT, cnt);
+    if (ev) HIPCHK(c, hipEventRecord(ev[0], st));
+    GC_LAUNCH(K.scan, g.nFrames, 1024, st, cnt, g.tilesPerFrame);
+    if (ev) HIPCHK(c, hipEventRecord(ev[1], st));
+    GC_LAUNCH(K.scatter[pass], perT * GC_XCDS, g.scatterT, st, src, (uint64_t)n, frameArg, g.nTiles, perT, (const uint32_t*)cnt, ent);
+    if (ev) HIPCHK(c, hipEventRecord(ev[2], st));
+    GC_LAUNCH(K.link, linkGrid, 64, st, (const uint32_t*)cnt, (const GcMfEntry*)ent, ent2, g.tilesPerFrame, g.frameBytes, nLists, ticket);
+    if (ev) HIPCHK(c, hipEventRecord(ev[3], st));
+    return GC_OK;
+}
+
 // Match finder for one part of the input: `src` / `n` are the part, blk0 its first block (a multiple of frameBlocks: parts are
 // whole frames, so everything inside is relative to the part and only the workspace pointers are offset).
 static int launch_finder_part(gc_ctx* c, const GcLzPlan& plan, hipStream_t st, uint32_t part, const uint8_t* src, size_t n, uint32_t frameArg /* F, or F | S << 8 | C << 16: overlapping frames (gc_mf.h) */, uint32_t blk0, unsigned long long* prof)
@@ -582,23 +526,18 @@ static int launch_finder_part(gc_ctx* c, const GcLzPlan& plan, hipStream_t st, u
         GC_LAUNCH(gc_zstd_lz_kernel, nBlocks, 1024, st, src, (uint64_t)n, seqRaw, lit, meta, prof);
         return GC_OK;
     }
-    const GcMfGeom g = gc_mf_geom(n, frameBlocks, plan.mfFast != 0u);
+    const bool fast = plan.mfFast != 0u;
+    const GcMfKernels& K = fast ? kFast : kWide;                           // the kernels of this geometry
+    const GcMfGeom g = gc_mf_geom(n, frameBlocks, fast);
     const uint32_t frame0 = (blk0 / groupBlocks) * MF_FPG(frameArg);       // (parts are whole groups)
     uint32_t* cnt = c->mfCnt;                                              // count table and entry lists: every part from their start (ensure_finder_workspace)
     GcMfEntry* ent = c->mfEnt;
     GcMfEntry* ent2 = c->mfEnt2;
     uint32_t* rec = c->mfRec + (size_t)blk0 * GC_ZSTD_BLOCK_MAX;
     const uint32_t perT = gc_xcd_per(g.nTiles), perB = gc_xcd_per(nBlocks);
-    const bool fast = plan.mfFast != 0u;
-    const uint32_t nParts = 1u << g.partLog;
-#define MFSEL(k) (fast ? k##_p8 : k)          // the kernel of this geometry
-    // W4 is a persistent launch: one-wave workgroups, six per CU (24 KiB of LDS each), fed from a ticket counter (one counter per launch and part)
+    uint32_t* const tickets = c->mfTicket + part * 16u;                    // words 0..3: W4's launches, 8..15: the fused kernel's XCD classes
     uint32_t linkLaunch = 0;
-    const uint32_t linkWpc = 6u;
-    const uint32_t nLists = g.nFrames * nParts, linkGrid = nLists * GC_MF_LINK_SEGS < c->nCU * linkWpc ? nLists * GC_MF_LINK_SEGS : c->nCU * linkWpc;
-    HIPCHK(c, hipMemsetAsync(c->mfTicket + part * 16u, 0, 16u * sizeof(uint32_t), st));      // words 0..3: W4's launches, 8..15: the fused kernel's XCD classes
-#define MF_LINK(cnt_, ent_, ent2_) do { uint32_t* ticket_ = c->mfTicket + part * 16u + linkLaunch++; \
-        GC_LAUNCH(MFSEL(gc_mf_link_kernel), linkGrid, 64, st, (const uint32_t*)(cnt_), (const GcMfEntry*)(ent_), ent2_, g.tilesPerFrame, g.frameBytes, nLists, ticket_); } while (0)
+    HIPCHK(c, hipMemsetAsync(tickets, 0, 16u * sizeof(uint32_t), st));
     hipEvent_t* ev = c->evMf[part];
     HIPCHK(c, hipEventRecord(ev[0], st));
     // W5s reads nothing but the input: it runs beside the finder's passes on the context's second stream (round 5; it was 1.5 ms of the main stream's chain per 212 MB).  stream2 is
@@ -610,55 +549,38 @@ static int launch_finder_part(gc_ctx* c, const GcLzPlan& plan, hipStream_t st, u
         GC_LAUNCH(gc_mf_short_kernel, perC * GC_XCDS, 256, c->stream2, src, (uint64_t)n, groupBlocks, (uint32_t)((n + 2047u) / 2048u), perC, c->mfRec3 + (size_t)blk0 * GC_ZSTD_BLOCK_MAX);
         HIPCHK(c, hipEventRecord(c->evShort[part], c->stream2));
     }
-    GC_LAUNCH(MFSEL(gc_mf_count_kernel), perT * GC_XCDS, nParts, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, cnt);
-    HIPCHK(c, hipEventRecord(ev[1], st));
-    GC_LAUNCH(MFSEL(gc_mf_scan_kernel), g.nFrames, 1024, st, cnt, g.tilesPerFrame);
-    HIPCHK(c, hipEventRecord(ev[2], st));
-    GC_LAUNCH(MFSEL(gc_mf_scatter_kernel), perT * GC_XCDS, g.scatterT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt, ent);
-    HIPCHK(c, hipEventRecord(ev[3], st));
-    MF_LINK(cnt, ent, ent2);
-    HIPCHK(c, hipEventRecord(ev[4], st));
+    int rc = mf_list_pass(c, K, st, MF_BASE, g, frameBlocks, src, n, cnt, ent, ent2, tickets + linkLaunch++, ev + 1);      // (events 1..4)
+    if (rc != GC_OK) return rc;
     // the levels that parse the first pass's records as they are: verify + parse in one kernel, the records stay in LDS (W5 + W6 fused)
     const bool fused = !plan.farPass && !plan.farPass2 && !plan.searchDepth && !plan.priceParse && !plan.shortPass && MF_C(frameArg) == MF_F(frameArg);
     if (fused) {
-        {
-            const uint32_t tpb = GC_ZSTD_BLOCK_MAX >> g.tileLog;
-            const uint32_t perV = ((gc_xcd_per(g.nTiles) + tpb - 1u) / tpb) * tpb;      // whole blocks per XCD class: a tile never waits for a tile of another class
-            uint32_t* tw = c->mfTileWord + (size_t)frame0 * g.tilesPerFrame;
-            HIPCHK(c, hipMemsetAsync(tw, 0, (size_t)g.nTiles * sizeof(uint32_t), st));
-            GC_LAUNCH(MFSEL(gc_mf_vparse_tile_kernel), perV * GC_XCDS, g.verifyT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perV, plan.lazyDepth, (const uint32_t*)cnt,
-                      (const GcMfEntry*)ent2, seqRaw, lit, meta, c->mfTicket + part * 16u + 8u, tw, prof);
-        }
+        const uint32_t tpb = GC_ZSTD_BLOCK_MAX >> g.tileLog;
+        const uint32_t perV = ((gc_xcd_per(g.nTiles) + tpb - 1u) / tpb) * tpb;      // whole blocks per XCD class: a tile never waits for a tile of another class
+        uint32_t* tw = c->mfTileWord + (size_t)frame0 * g.tilesPerFrame;
+        HIPCHK(c, hipMemsetAsync(tw, 0, (size_t)g.nTiles * sizeof(uint32_t), st));
+        GC_LAUNCH(K.vparseTile, perV * GC_XCDS, g.verifyT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perV, plan.lazyDepth, (const uint32_t*)cnt,
+                  (const GcMfEntry*)ent2, seqRaw, lit, meta, tickets + 8u, tw, prof);
         for (int i = 10; i <= 12; i++) HIPCHK(c, hipEventRecord(ev[i], st));
         HIPCHK(c, hipEventRecord(ev[5], st));
         HIPCHK(c, hipEventRecord(ev[6], st));
-        (void)prof;
         return GC_OK;
     }
-    GC_LAUNCH(MFSEL(gc_mf_verify_kernel), perT * GC_XCDS, g.verifyT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt,
-                   (const GcMfEntry*)ent2, rec);
+    GC_LAUNCH(K.verify[MF_BASE], perT * GC_XCDS, g.verifyT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt, (const GcMfEntry*)ent2, rec);
     HIPCHK(c, hipEventRecord(ev[10], st));
-    if (plan.farPass) {                                         // second pass with 16- / 12-byte keys, merged into rec (timed with W5)
-        GC_LAUNCH(MFSEL(gc_mf_count_far_kernel), perT * GC_XCDS, nParts, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, cnt);
-        GC_LAUNCH(MFSEL(gc_mf_scan_kernel), g.nFrames, 1024, st, cnt, g.tilesPerFrame);
-        GC_LAUNCH(MFSEL(gc_mf_scatter_far_kernel), perT * GC_XCDS, g.scatterT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt, ent);
-        MF_LINK(cnt, ent, ent2);
-        GC_LAUNCH(MFSEL(gc_mf_verify_far_kernel), perT * GC_XCDS, g.verifyT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt,
-                  (const GcMfEntry*)ent2, rec);
-    }
-    if (plan.farPass2) {                                        // third pass of the far kind: keys of 32 / 24 bytes, capped records ranked by what lies behind the cap (gc_lz_window.hip MF_FAR2; timed with W5)
-        GC_LAUNCH(MFSEL(gc_mf_count_far2_kernel), perT * GC_XCDS, nParts, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, cnt);
-        GC_LAUNCH(MFSEL(gc_mf_scan_kernel), g.nFrames, 1024, st, cnt, g.tilesPerFrame);
-        GC_LAUNCH(MFSEL(gc_mf_scatter_far2_kernel), perT * GC_XCDS, g.scatterT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt, ent);
-        MF_LINK(cnt, ent, ent2);
-        GC_LAUNCH(MFSEL(gc_mf_verify_far2_kernel), perT * GC_XCDS, g.verifyT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt,
-                  (const GcMfEntry*)ent2, rec);
+    // second pass with 16- / 12-byte keys, merged into rec; third pass of the far kind: keys of 32 / 24 bytes, capped records ranked by what lies behind the cap
+    // (gc_lz_window.hip MF_FAR2).  Both are timed with W5.
+    const int farPasses[2] = { plan.farPass ? MF_FAR : -1, plan.farPass2 ? MF_FAR2 : -1 };
+    for (const int pass : farPasses) {
+        if (pass < 0) continue;
+        rc = mf_list_pass(c, K, st, pass, g, frameBlocks, src, n, cnt, ent, ent2, tickets + linkLaunch++, nullptr);
+        if (rc != GC_OK) return rc;
+        GC_LAUNCH(K.verify[pass], perT * GC_XCDS, g.verifyT, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)cnt, (const GcMfEntry*)ent2, rec);
     }
     HIPCHK(c, hipEventRecord(ev[11], st));
     uint32_t* const chg = (plan.searchDepth && plan.shortPass && plan.priceParse) ? c->mfChanged + (size_t)blk0 * (GC_ZSTD_BLOCK_MAX / 32u) : (uint32_t*)nullptr;      // which records W5b changes: what the pass with 4- / 3-byte keys looks at again (gc_lz_window.hip "continuation")
     if (plan.searchDepth) {                                     // W5b: follow match links (timed with W5)
         uint32_t* rec2 = c->mfRec2 + (size_t)blk0 * GC_ZSTD_BLOCK_MAX;
-        GC_LAUNCH(MFSEL(gc_mf_deepen_kernel), perT * GC_XCDS, 256, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, plan.searchDepth | (plan.searchShallow << 8), (const uint32_t*)rec, rec2, chg);
+        GC_LAUNCH(K.deepen, perT * GC_XCDS, 256, st, src, (uint64_t)n, frameBlocks, g.nTiles, perT, plan.searchDepth | (plan.searchShallow << 8), (const uint32_t*)rec, rec2, chg);
         rec = rec2;
     }
     HIPCHK(c, hipEventRecord(ev[12], st));
@@ -669,19 +591,13 @@ static int launch_finder_part(gc_ctx* c, const GcLzPlan& plan, hipStream_t st, u
         // Overlapping frames list and link every position once per frame that holds it.  A match of 3-4 bytes MiBs back is never worth its distance, so this pass runs
         // over frames that tile the input (the plain geometry F: a frame then lies inside its group, whose start is as far back as the stages behind the finder let a match reach)
         const uint32_t fbS = plan.shortPlain ? MF_F(frameArg) : frameArg;               // (flzma2_plan: which levels keep the overlap)
-        const GcMfGeom gs = gc_mf_geom(n, fbS, plan.mfFast != 0u);
-        const uint32_t perTs = gc_xcd_per(gs.nTiles), nListsS = gs.nFrames * nParts;
-        uint32_t* cntS = c->mfCnt;
-        GC_LAUNCH(MFSEL(gc_mf_count_short_kernel), perTs * GC_XCDS, nParts, st, src, (uint64_t)n, fbS, gs.nTiles, perTs, cntS);
-        GC_LAUNCH(MFSEL(gc_mf_scan_kernel), gs.nFrames, 1024, st, cntS, gs.tilesPerFrame);
-        GC_LAUNCH(MFSEL(gc_mf_scatter_short_kernel), perTs * GC_XCDS, gs.scatterT, st, src, (uint64_t)n, fbS, gs.nTiles, perTs, (const uint32_t*)cntS, ent);
-        {   uint32_t* ticket_ = c->mfTicket + part * 16u + linkLaunch++;
-            const uint32_t gridS = nListsS * GC_MF_LINK_SEGS < c->nCU * linkWpc ? nListsS * GC_MF_LINK_SEGS : c->nCU * linkWpc;
-            GC_LAUNCH(MFSEL(gc_mf_link_kernel), gridS, 64, st, (const uint32_t*)cntS, (const GcMfEntry*)ent, ent2, gs.tilesPerFrame, gs.frameBytes, nListsS, ticket_); }
-        if (plan.shortPlain) GC_LAUNCH(MFSEL(gc_mf_verify_short_kernel), perTs * GC_XCDS, gs.verifyT, st, src, (uint64_t)n, fbS, gs.nTiles, perTs, (const uint32_t*)cntS,
+        const GcMfGeom gs = gc_mf_geom(n, fbS, fast);
+        const uint32_t perTs = gc_xcd_per(gs.nTiles);
+        rc = mf_list_pass(c, K, st, MF_SHORT, gs, fbS, src, n, cnt, ent, ent2, tickets + linkLaunch++, nullptr);
+        if (rc != GC_OK) return rc;
+        const auto verifyK = plan.shortPlain ? K.verifyShort : K.verifyShortB;          // (B: with the catch-up, gc_lz_window.hip)
+        GC_LAUNCH(verifyK, perTs * GC_XCDS, gs.verifyT, st, src, (uint64_t)n, fbS, gs.nTiles, perTs, (const uint32_t*)cnt,
                   (const GcMfEntry*)ent2, (const uint32_t*)rec, recN, (const uint32_t*)chg);
-        else GC_LAUNCH(MFSEL(gc_mf_verify_shortb_kernel), perTs * GC_XCDS, gs.verifyT, st, src, (uint64_t)n, fbS, gs.nTiles, perTs, (const uint32_t*)cntS,
-                  (const GcMfEntry*)ent2, (const uint32_t*)rec, recN, (const uint32_t*)chg);      // (with the catch-up: gc_lz_window.hip)
         recDp = recN;
     }
     HIPCHK(c, hipEventRecord(ev[5], st));
@@ -706,6 +622,10 @@ static int launch_finder_part(gc_ctx* c, const GcLzPlan& plan, hipStream_t st, u
         if (plan.laneDp) GC_LAUNCH(gc_mf_litprice_kernel, perB * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perB, (const uint16_t*)price, litCtxArg, lpr);
         // (Round 5 built a re-priced SECOND pass over every window -- the first full pass counts its own paths, the second prices from those counts -- behind a hook: text -0.14 .. -0.25 %,
         //  real sources +1.6 %, FLZMA2 on shared objects -0.04 %, profiles/r05_zstd19.md.  Measured, not taken; removed in round 6.)
+        // The kernels by the shortest piece: 2 bytes (LZMA), or 3 (zstd, and brotli with the ring's first entries standing in for zstd's repeat offsets).  W7L has a form of its own for phase A.
+        const bool min2 = plan.priceMinLen <= 2u;
+        const auto dpK = min2 ? gc_mf_dp2_kernel : gc_mf_dp3_kernel;
+        const decltype(&gc_mf_dpl2_kernel) dplK[2] = { min2 ? gc_mf_dpl2s_kernel : gc_mf_dplzs_kernel, min2 ? gc_mf_dpl2_kernel : gc_mf_dplz_kernel };      // [phase != A]
         for (uint32_t pass = plan.dpPhases == 1u ? 1u : 0u; pass < 2u; pass++) {
             const uint32_t phase = plan.dpPhases == 1u ? 2u : pass;      // (2: phase B under W6's prices)
             const uint32_t nDpWg = nBlocks * (phase == 0u ? 1u : 8u), perD = gc_xcd_per(nDpWg);
@@ -715,21 +635,12 @@ static int launch_finder_part(gc_ctx* c, const GcLzPlan& plan, hipStream_t st, u
                 const bool w2 = (plan.smallWin2k == 2u || (plan.smallWin2k == 1u && nBlocks <= 1024u)) && phase != 0u;
                 const uint32_t nItems = w2 ? nBlocks : (nBlocks + 1u) / 2u, perL = gc_xcd_per(nItems);     // a wave = two blocks (2 KiB windows: one)
                 const bool select = plan.laneDp == 2u && phase == 1u && !w2;
-                const uint32_t phaseK = phase | (w2 ? 16u : 0u) | (select ? GC_DP_SELECT : 0u) | (plan.allLengths ? GC_DP_ALLLEN : 0u);
-                if (select) {                                      // the blocks without repeats: W7
-                    if (plan.priceMinLen <= 2u) GC_LAUNCH(gc_mf_dp2_kernel, perD * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perD, groupBlocks, phaseK, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp);
-                    else GC_LAUNCH(gc_mf_dp3_kernel, perD * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perD, groupBlocks, phaseK, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp);
-                }
-                if (plan.priceMinLen <= 2u) {
-                    if (phase == 0u) GC_LAUNCH(gc_mf_dpl2s_kernel, perL * GC_XCDS, GC_DPL_THREADS, st, src, (uint64_t)n, nBlocks, perL, groupBlocks, phase | (plan.allLengths ? GC_DP_ALLLEN : 0u), dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp, (const uint8_t*)lpr);
-                    else GC_LAUNCH(gc_mf_dpl2_kernel, perL * GC_XCDS, GC_DPL_THREADS, st, src, (uint64_t)n, nBlocks, perL, groupBlocks, phaseK, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp, (const uint8_t*)lpr);
-                } else {                                           // zstd, and brotli with the ring's first entries standing in for zstd's repeat offsets
-                    if (phase == 0u) GC_LAUNCH(gc_mf_dplzs_kernel, perL * GC_XCDS, GC_DPL_THREADS, st, src, (uint64_t)n, nBlocks, perL, groupBlocks, phase | (plan.allLengths ? GC_DP_ALLLEN : 0u), dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp, (const uint8_t*)lpr);
-                    else GC_LAUNCH(gc_mf_dplz_kernel, perL * GC_XCDS, GC_DPL_THREADS, st, src, (uint64_t)n, nBlocks, perL, groupBlocks, phaseK, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp, (const uint8_t*)lpr);
-                }
+                const uint32_t phaseK = phase | (w2 ? 16u : 0u) | (select ? GC_DP_SELECT : 0u) | (plan.allLengths ? GC_DP_ALLLEN : 0u);      // (phase A: neither 2 KiB windows nor a selection)
+                if (select)                                        // the blocks without repeats: W7
+                    GC_LAUNCH(dpK, perD * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perD, groupBlocks, phaseK, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp);
+                GC_LAUNCH(dplK[phase != 0u], perL * GC_XCDS, GC_DPL_THREADS, st, src, (uint64_t)n, nBlocks, perL, groupBlocks, phaseK, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp, (const uint8_t*)lpr);
             } else
-            if (plan.priceMinLen <= 2u) GC_LAUNCH(gc_mf_dp2_kernel, perD * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perD, groupBlocks, phase, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp);
-            else GC_LAUNCH(gc_mf_dp3_kernel, perD * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perD, groupBlocks, phase, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp);
+                GC_LAUNCH(dpK, perD * GC_XCDS, 256, st, src, (uint64_t)n, nBlocks, perD, groupBlocks, phase, dps, litCtxArg, recDp, (const uint16_t*)rec3, (const uint16_t*)price, dp, wcp);
         }
         HIPCHK(c, hipEventRecord(ev[9], st));
         GC_LAUNCH(gc_mf_parse_kernel, perB * GC_XCDS, GC_MF_PARSE_T, st, src, (uint64_t)n, nBlocks, perB, 0u, (const uint32_t*)dp, seqRaw, lit, meta, (uint16_t*)nullptr, 0u);
@@ -741,7 +652,6 @@ static int launch_finder_part(gc_ctx* c, const GcLzPlan& plan, hipStream_t st, u
     else
         GC_LAUNCH(gc_mf_parse_kernel, perB * GC_XCDS, GC_MF_PARSE_T, st, src, (uint64_t)n, nBlocks, perB, plan.lazyDepth, (const uint32_t*)rec, seqRaw, lit, meta, (uint16_t*)nullptr, 0u);
     HIPCHK(c, hipEventRecord(ev[6], st));
-    (void)prof;
     return GC_OK;
 }
 
@@ -1011,13 +921,13 @@ extern "C" int gc_test_wave_scans(gc_ctx* c, const uint32_t* v, const uint64_t* 
     return GC_OK;
 }
 
-// Test entry (the test builds only): W1..W3 of ONE key mode (0 base, 1 far, 2 short, 4 far2: gc_lz_window.hip MF_*) and one geometry over frames of frameBlocks blocks
+// Test entry (the test builds only): W1..W3 of ONE key mode (0 base, 1 far, 2 short, 4 far2: gc_mf.h MF_*) and one geometry over frames of frameBlocks blocks
 // (2..64, no overlap), so that a test sees the lists themselves -- which of W1 and W3 disagrees with a model, where a stream hash only says that something does.
 // HOST memory throughout: src[n] is copied to the device; offs receives the offsets table after W2 (gc_mf_geom(n, frameBlocks, fast).cntWords words: [frame][tile 0 ..
 // tilesPerFrame][partition]), ent the entry array after W3 (nFrames * frameBlocks * 128 Ki entries; what lies outside the runs is 0xFF bytes).
 extern "C" int gc_test_mf_lists(gc_ctx* c, const uint8_t* src, size_t n, int fast, int mode, uint32_t frameBlocks, uint32_t* offs, uint64_t* ent)
 {
-    if (!c || !src || !n || !offs || !ent || frameBlocks < 2u || frameBlocks > GC_MF_MAX_FRAME_BLOCKS || (mode != 0 && mode != 1 && mode != 2 && mode != 4)) return GC_ERR_PARAM;
+    if (!c || !src || !n || !offs || !ent || frameBlocks < 2u || frameBlocks > GC_MF_MAX_FRAME_BLOCKS || (mode != MF_BASE && mode != MF_FAR && mode != MF_SHORT && mode != MF_FAR2)) return GC_ERR_PARAM;
     HIPCHK(c, hipSetDevice(c->device));
     const GcMfGeom g = gc_mf_geom(n, frameBlocks, fast != 0);
     const size_t cntBytes = (size_t)g.cntWords * sizeof(uint32_t), entBytes = (size_t)g.nFrames * g.frameBytes * sizeof(GcMfEntry), srcBytes = (n + 15u) & ~(size_t)15u;
@@ -1029,18 +939,10 @@ extern "C" int gc_test_mf_lists(gc_ctx* c, const uint8_t* src, size_t n, int fas
     hipError_t e = hipMemcpy(dSrc, src, n, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemsetAsync(dEnt, 0xFF, entBytes, st);
     if (e == hipSuccess) {
-#define MFT_LAUNCH(cntK, scatK) do { \
-        if (fast) { GC_LAUNCH(cntK##_p8, perT * GC_XCDS, nParts, st, (const uint8_t*)dSrc, (uint64_t)n, frameBlocks, g.nTiles, perT, dCnt); \
-                    GC_LAUNCH(gc_mf_scan_kernel_p8, g.nFrames, 1024, st, dCnt, g.tilesPerFrame); \
-                    GC_LAUNCH(scatK##_p8, perT * GC_XCDS, g.scatterT, st, (const uint8_t*)dSrc, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)dCnt, dEnt); } \
-        else      { GC_LAUNCH(cntK, perT * GC_XCDS, nParts, st, (const uint8_t*)dSrc, (uint64_t)n, frameBlocks, g.nTiles, perT, dCnt); \
-                    GC_LAUNCH(gc_mf_scan_kernel, g.nFrames, 1024, st, dCnt, g.tilesPerFrame); \
-                    GC_LAUNCH(scatK, perT * GC_XCDS, g.scatterT, st, (const uint8_t*)dSrc, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)dCnt, dEnt); } } while (0)
-        if (mode == 0) MFT_LAUNCH(gc_mf_count_kernel, gc_mf_scatter_kernel);
-        else if (mode == 1) MFT_LAUNCH(gc_mf_count_far_kernel, gc_mf_scatter_far_kernel);
-        else if (mode == 2) MFT_LAUNCH(gc_mf_count_short_kernel, gc_mf_scatter_short_kernel);
-        else MFT_LAUNCH(gc_mf_count_far2_kernel, gc_mf_scatter_far2_kernel);
-#undef MFT_LAUNCH
+        const GcMfKernels& K = fast ? kFast : kWide;                  // (W1..W3 as mf_list_pass launches them; W4 is not run: the test reads the lists W3 leaves)
+        GC_LAUNCH(K.count[mode], perT * GC_XCDS, nParts, st, (const uint8_t*)dSrc, (uint64_t)n, frameBlocks, g.nTiles, perT, dCnt);
+        GC_LAUNCH(K.scan, g.nFrames, 1024, st, dCnt, g.tilesPerFrame);
+        GC_LAUNCH(K.scatter[mode], perT * GC_XCDS, g.scatterT, st, (const uint8_t*)dSrc, (uint64_t)n, frameBlocks, g.nTiles, perT, (const uint32_t*)dCnt, dEnt);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1612,10 +1514,6 @@ static int stage_reserve(gc_ctx* c, size_t inBytes, size_t outBytes, size_t outP
 }
 
 struct GcStreamScope { hipStream_t prev; explicit GcStreamScope(hipStream_t st) : prev(gc_tls_stream) { gc_tls_stream = st; } ~GcStreamScope() { gc_tls_stream = prev; } };      // (gc_host_stream.h: the stand-alone entry points run on this context's stream while in scope)
-extern "C" int gc_crc32_device(const void* d_src, size_t n, uint32_t* crc);
-extern "C" int gc_bra_convert_device(int kind, const void* d_src, void* d_dst, size_t n, uint32_t pc, int encoding, size_t* processed);
-extern "C" int gc_bra_x86_convert_device(const void* d_src, void* d_dst, size_t n, uint32_t pc, int encoding, uint32_t* state, size_t* processed);
-extern "C" int gc_delta_convert_device(const void* d_src, void* d_dst, size_t n, unsigned delta, int encoding, unsigned char state[256]);
 
 // H2D + [CRC-32 of the raw bytes + pre-filter, both on the device: gpucodec.h gc_pre] + enqueue of the codec's kernels
 extern "C" int gc_host_begin_pre(gc_ctx* c, int codec, const void* src, size_t n, int level, unsigned flags, gc_pre* pre)
@@ -1708,22 +1606,6 @@ extern "C" size_t gc_codec_grain(int codec, int level)
 }
 
 // ---------------------------------------------------------------- ZSTD decoding ----------------------------------------------------------------
-extern "C" void gc_zstd_dec_launch_index(hipStream_t st, const uint8_t* src, const GcZdFrame* frames, uint32_t nFrames, GcZdBlock* blocks, uint64_t* frameTot);
-extern "C" void gc_zstd_dec_launch_literals(hipStream_t st, const uint8_t* src, uint64_t srcSize, const GcZdFrame* frames, GcZdBlock* blocks, uint32_t nBlocks, uint8_t* litWork,
-                                            unsigned long long* prof, const uint32_t* order, uint32_t* ready);
-extern "C" void gc_zstd_dec_launch_sequences(hipStream_t st, const uint8_t* src, uint64_t srcSize, const GcZdFrame* frames, GcZdBlock* blocks, uint32_t nBlocks, void* seqWork,
-                                             unsigned long long* prof, const uint32_t* order, uint32_t* ready, int several);
-extern "C" void gc_zstd_dec_launch_exec(hipStream_t st, const uint8_t* src, uint64_t srcSize, uint8_t* dst, uint64_t dstCap, const GcZdFrame* frames, uint32_t nFrames,
-                                        GcZdBlock* blocks, uint32_t* ticket, uint8_t* litWork, uint64_t litWorkSize, void* seqWork, uint64_t* result, unsigned long long* prof,
-                                        const uint32_t* ready, const uint8_t* dict, uint32_t dictSize);
-
-extern "C" void gc_zstd_dec_launch_place(hipStream_t st, const GcZdFrame* frames, uint32_t nFrames, const GcZdBlock* blocks, uint64_t dstCap, GcZdPlace* place, uint64_t* result, uint32_t* ferr);
-extern "C" void gc_zstd_dec_launch_spread(hipStream_t st, const uint8_t* src, uint64_t srcSize, uint8_t* dst, const GcZdFrame* frames, const GcZdBlock* blocks, uint32_t nBlocks,
-                                          const GcZdPlace* place, const uint8_t* litWork, uint64_t litWorkSize, const void* seqWork, uint32_t* ptr, uint64_t batchBase, uint32_t* ferr,
-                                          const uint8_t* dict, uint32_t dictSize);
-extern "C" void gc_zstd_dec_launch_chase(hipStream_t st, uint8_t* dstBatch, uint32_t* ptr, uint32_t n, uint32_t hops, uint8_t* pieceDone, uint32_t* counter);
-extern "C" void gc_zstd_dec_launch_finish(hipStream_t st, const uint8_t* src, const uint8_t* dst, const GcZdFrame* frames, uint32_t nFrames, uint64_t* result, const uint32_t* ferr);
-
 // the zstd decoder's arrays grow with an eighth to spare: batches of about the same size follow each other
 static int zd_reserve(gc_ctx* c, GcBufRaw& b, size_t need)
 {

@@ -12,3 +12,6 @@ struct GcBrDecWork {
     uint32_t ldsCap = 0;                  // test hook (GC_BRD_LDS): a smaller LDS arena, so that small inputs take the HBM pages; 0 = the kernel's own
     void* ev0 = nullptr; void* ev1 = nullptr; float ms = 0.f;       // HIP events around the kernels of the last call
 };
+// gc_brotli_dec.hip, called by the context's entry points (gc_api.hip)
+void gc_brd_release(GcBrDecWork* w);
+int gc_brd_decode(hipStream_t st, GcBrDecWork* w, const uint8_t* d_src, const gc_brotli_chunk* chunks, size_t nChunks, uint8_t* d_dst, size_t dstCap, size_t* produced, char* err, size_t errCap);

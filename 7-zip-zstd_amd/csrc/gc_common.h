@@ -18,6 +18,7 @@
 // format-normative step is reproduced exactly so that the reference decoder regenerates the input.
 #pragma once
 #include <stdint.h>
+#include "gpucodec.h"      // gc_batch_item, gc_batch_result
 
 #define GC_ZSTD_BLOCK_MAX   (128u * 1024u)   // zstd block size limit (ZSTD_BLOCKSIZE_MAX)
 #define GC_MIN_MATCH        5u               // shortest match the finder emits
@@ -40,6 +41,8 @@ struct GcSectionInfo {
     uint32_t nSeq;         // merged sequence count (diagnostics)
     uint32_t flags;        // bit0: literals stored raw, bit1: literals RLE
 };
+// K4 -> K5, per block: where its bytes go in the output, how many, and whether they are the compressed form
+struct GcFramePlan { uint64_t off; uint32_t size; uint32_t compressed; };
 
 // per-block strides of the section staging buffers
 #define GC_LITSEC_STRIDE (GC_ZSTD_BLOCK_MAX + 64u)
@@ -71,3 +74,24 @@ struct GcSeqTabG {                                                // K3b -> K3c,
 };
 
 static inline uint32_t gc_num_blocks(uint64_t n) { return (uint32_t)((n + GC_ZSTD_BLOCK_MAX - 1) / GC_ZSTD_BLOCK_MAX); }
+
+// The kernels of the stages above, declared ONCE: the file that defines a kernel and the host code that launches it (gc_api.hip) both see this prototype, so a
+// definition that stops matching it is a compile error ("conflicting types") instead of a launch with a wrong argument block.
+extern "C" __global__ void gc_zstd_lz_kernel(const uint8_t*, uint64_t, GcSeqRaw*, uint8_t*, GcBlockMeta*, unsigned long long*);
+extern "C" __global__ void gc_zstd_huf_kernel(const uint8_t*, const GcBlockMeta*, uint8_t*, GcSectionInfo*);
+extern "C" __global__ void gc_zstd_seq_codes_kernel(const GcSeqRaw*, const GcBlockMeta*, uint64_t*, uint32_t*, uint8_t*, GcSeqHist*, uint8_t*, GcSectionInfo*, uint32_t, unsigned long long*);
+extern "C" __global__ void gc_zstd_seq_tables_kernel(const GcSeqHist*, const GcSectionInfo*, GcSeqTabG*, unsigned long long*);
+extern "C" __global__ void gc_zstd_seq_chain_kernel(const uint8_t*, const GcSectionInfo*, GcSeqTabG*, uint16_t*, unsigned long long*);
+extern "C" __global__ void gc_zstd_seq_pack_kernel(const uint64_t*, const uint8_t*, const uint16_t*, const GcSeqTabG*, uint8_t*, GcSectionInfo*, uint64_t, unsigned long long*);
+extern "C" __global__ void gc_wave_scan_test_kernel(const uint32_t*, const uint64_t*, uint32_t*, uint32_t*, uint64_t*);      // (gc_zstd_seq.hip; launched by gc_test_wave_scans only)
+extern "C" __global__ void gc_zstd_plan_kernel(const GcSectionInfo*, uint32_t, uint64_t, uint64_t, uint32_t, GcFramePlan*, uint64_t*, uint32_t, uint32_t);
+extern "C" __global__ void gc_zstd_emit_kernel(const uint8_t*, uint64_t, const uint8_t*, const uint8_t*, const GcSectionInfo*, const GcFramePlan*, const uint64_t*, uint32_t, uint32_t, uint8_t*, const uint64_t*);
+extern "C" __global__ void gc_zstd_xxh64_kernel(const uint8_t*, uint64_t, uint64_t, uint32_t, uint64_t, uint64_t*);      // K0x (gc_xxh64.h)
+// the batch forms of K1, K3d, K4, K5 and K0x: an item table where the others derive a block's place and length from the stream's size (gc_zstd_batch.h)
+extern "C" __global__ void gc_zstd_lz_batch_kernel(const uint8_t*, const gc_batch_item*, GcSeqRaw*, uint8_t*, GcBlockMeta*);
+extern "C" __global__ void gc_zstd_lz_batch_dict_kernel(const uint8_t*, const gc_batch_item*, GcSeqRaw*, uint8_t*, GcBlockMeta*, const uint8_t*, uint32_t, const uint32_t*, const uint32_t*);
+extern "C" __global__ void gc_zstd_dict_digest_kernel(const uint8_t*, uint32_t, uint32_t*, uint32_t*);
+extern "C" __global__ void gc_zstd_seq_pack_batch_kernel(const uint64_t*, const uint8_t*, const uint16_t*, const GcSeqTabG*, uint8_t*, GcSectionInfo*, const gc_batch_item*);
+extern "C" __global__ void gc_zstd_plan_batch_kernel(const GcSectionInfo*, const gc_batch_item*, uint32_t, uint64_t, GcFramePlan*, gc_batch_result*, uint64_t*, uint32_t);
+extern "C" __global__ void gc_zstd_emit_batch_kernel(const uint8_t*, const gc_batch_item*, const uint8_t*, const uint8_t*, const GcSectionInfo*, const GcFramePlan*, const uint64_t*, uint8_t*, const uint64_t*);
+extern "C" __global__ void gc_zstd_xxh64_batch_kernel(const uint8_t*, const gc_batch_item*, uint64_t*);

@@ -26,15 +26,19 @@
 #include <stdlib.h>
 #endif
 
-// kernel names of this geometry (gc_mf.h: the fast geometry is compiled from gc_lz_window_p8.hip with the suffix _p8)
+// kernel names of this geometry (the fast geometry is compiled from gc_lz_window_p8.hip with the suffix _p8).  Both sets of names are declared in gc_mf.h
+// (GC_MF_GEOM_KERNELS): a kernel added or changed here changes there, in the one list that also fills the host's kernel tables.
 #ifdef GC_MF_FAST
 #define MFK(name) name##_p8
+#define MFK_PROTOTYPES GC_MF_GEOM_KERNELS(GC_MF_DECLARE, _p8)
 #else
 #define MFK(name) name
+#define MFK_PROTOTYPES GC_MF_GEOM_KERNELS(GC_MF_DECLARE, ) GC_MF_W6_KERNELS
 #endif
 
 // everything below depends on the geometry: one namespace per geometry, so that the two copies of the helpers never meet at link time
 namespace MFK(gc_mf_ns) {
+MFK_PROTOTYPES      // once more in the scope of the definitions: g++ (the emulator build) only warns where an extern "C" definition in a namespace disagrees with a prototype at global scope, and rejects one that disagrees with a prototype of its own scope, as hipcc does with both
 
 #define MF_T         GC_MF_PARTS      // W1: threads per tile (one per partition)
 static_assert(MF_T == GC_MF_PARTS, "W1 uses one thread per partition for the histogram row");
@@ -115,13 +119,10 @@ __device__ __forceinline__ uint32_t mf_lds_byte(const uint32_t* sW, uint32_t i) 
 // occurrence of a position's first 4 / 3 bytes anywhere in the frame -- the short matches that the reference's structures
 // deliver at every position (2-byte radix heads radix_engine.h:106-171; ZSTD's hash3 table zstd_opt.c:408) and that pay where
 // literals are expensive.  Its records (lengths from 3) only feed the price-based parse W7.
-#define MF_BASE  0
-#define MF_FAR   1
-#define MF_SHORT 2
+// (The pass numbers MF_BASE / MF_FAR / MF_SHORT / MF_FAR2: gc_mf.h, where the host's kernel table is indexed by them.)
 // MF_FAR2 = one more pass of the far kind with keys of 32 ("long") and 24 ("short") bytes (round 5: zstd levels >= 7; round 6: >= 5; FLZMA2 levels >= 7): in data made of many near-copies of
 // the same text (source trees, archives of similar files) the most recent position with the same 16 bytes is often a copy that diverges a few dozen bytes later, where the
 // reference's chains and trees return the LONGEST match (real sources, zstd level 9 and 19: 1.12 x the reference with 10 % more sequences of the same cost each).
-#define MF_FAR2  4
 // Which positions of a tile are listed: tile-uniform, computed once per workgroup from scalar values.
 struct MfList {
     uint32_t limit;                   // tile positions q < limit exist and have a full compare window left in the frame

@@ -1,6 +1,7 @@
 // gc_lzma2.h -- shared definitions of the FLZMA2 (LZMA2) GPU path.
 #pragma once
 #include <stdint.h>
+#include "gc_common.h"
 
 #define GC_LZMA_LC 3u                       // lc=3 lp=0 pb=2: the reference's defaults (fl2_compress.c:116-138)
 #define GC_LZMA_LP 0u
@@ -61,3 +62,12 @@ struct GcLzmaChunkInfo { uint32_t usize; uint32_t csize; uint32_t wordStart; uin
 // words of (p, bit) stream reserved per segment: a literal is the densest symbol (9 coded bits per byte); keeps 16-byte alignment
 #define GC_LZMA_STREAM_WORDS(segLog) ((9u << (segLog)) + 64u)
 struct GcLzmaPlan { uint64_t off; uint32_t size; uint32_t kind; };   // kind 0 absent, 1 LZMA, 2 raw
+
+// The kernels (gc_lzma2_enc.hip: prep, model; gc_lzma2_frame.hip: the rest), declared once for their definitions and for the launches of gc_api.hip (gc_common.h)
+extern "C" __global__ void gc_lzma2_prep_kernel(const GcSeqRaw*, const GcBlockMeta*, uint64_t, uint64_t*, uint32_t*);
+extern "C" __global__ void gc_lzma2_model_kernel(const uint8_t*, uint64_t, const uint64_t*, const uint32_t*, uint32_t, uint32_t, uint16_t*, GcLzmaChunkInfo*, const uint32_t*, unsigned long long*, uint32_t, uint32_t, uint32_t, uint8_t*, uint32_t, uint32_t, uint32_t);
+extern "C" __global__ void gc_lzma2_segkind_kernel(const GcLzmaChunkInfo*, const uint8_t*, uint32_t, uint32_t, uint8_t*);
+extern "C" __global__ void gc_lzma2_rc_kernel(uint16_t*, uint32_t, uint32_t, uint8_t*, GcLzmaChunkInfo*);
+extern "C" __global__ void gc_lzma2_rc_fin_kernel(const uint16_t*, uint32_t, uint32_t, uint8_t*, GcLzmaChunkInfo*);
+extern "C" __global__ void gc_lzma2_plan_kernel(const GcLzmaChunkInfo*, uint32_t, uint32_t, uint64_t, uint32_t, GcLzmaPlan*, uint64_t*, const uint8_t*, const uint8_t*);
+extern "C" __global__ void gc_lzma2_emit_kernel(const uint8_t*, uint32_t, const uint8_t*, const GcLzmaChunkInfo*, const GcLzmaPlan*, uint32_t, uint32_t, const uint64_t*, uint8_t*, const uint8_t*);

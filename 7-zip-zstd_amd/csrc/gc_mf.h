@@ -30,7 +30,7 @@
 #include "gc_common.h"
 
 // Two geometries, compiled as two sets of W1..W5 kernels from the one source (gc_lz_window.hip; gc_lz_window_p8.hip defines GC_MF_FAST
-// and includes it: the kernels get the suffix _p8):
+// and includes it: the kernels get the suffix _p8; both sets are declared below, GC_MF_GEOM_KERNELS):
 //   wide  1024 partitions, 16 KiB tiles: 2^22 + 2^21 table slots per frame -- the levels that search far (FLZMA2, zstd >= 7, brotli >= 5)
 //   fast   256 partitions,  8 KiB tiles: 2^20 + 2^19 slots per frame (still 8 x the reference's level-3 tables, clevels.h:31) -- zstd 3-6,
 //          brotli 3-4; W3..W5 take 20 % less time for 1.3 % more size (run r2_b: 1 GB of text, 34.3 -> 27.4 ms of finder)
@@ -167,6 +167,57 @@ static inline GcMfGeom gc_mf_geom(uint64_t n, uint32_t frameArg, bool fast)
 #define GC_DP_ALLLEN    128u              // W7L (zstd): every length of a candidate is an edge, not only the short ones and the last four (gc_lz_dpl.hip relax())
 #define GC_DPS_RICH(C)  ((C)[GC_DPS_NMAT] != 0u && ((C)[GC_DPS_NREP] + (C)[GC_DPS_NSREP] + (C)[GC_DPS_NREP1] + (C)[GC_DPS_NREP2] + (C)[GC_DPS_NREP3]) * 20u >= (C)[GC_DPS_NMAT])
 #define GC_SHORT_NONE   0xFFFFu            // W5s -> W7: uint16 per position, (distance - 1) << 4 | (length - 2), or none
+
+// The kernels of the finder and the parses, declared ONCE for the files that define them and for the launches of gc_api.hip (gc_common.h).
+// Passes of W1..W5 = which keys a position is listed under (gc_lz_window.hip mf_keys): a pass has a count, a scatter and a verify kernel of its own and shares scan and
+// link with the others.  The numbers index the host's kernel tables (gc_api.hip GcMfKernels) and are the `mode` of the test entry gc_test_mf_lists.
+#define MF_BASE  0      // long key 8 bytes, short key 5
+#define MF_FAR   1      // 16 / 12 bytes, merged into the records of the base pass
+#define MF_SHORT 2      // 4 / 3 bytes (the levels with the price-based parse)
+#define MF_FAR2  4      // 32 / 24 bytes
+#define MF_PASSES 5     // (entries of a table indexed by pass; 3 is no pass)
+// The 17 kernels that exist once per geometry: X(slot of the host's table, kernel, parameters); S = nothing (wide, gc_lz_window.hip) or _p8 (fast, gc_lz_window_p8.hip).
+// No parameter type depends on the geometry.
+#define GC_MF_COUNT_ARGS  (const uint8_t* src, uint64_t srcSize, uint32_t frameArg, uint32_t nTiles, uint32_t per, uint32_t* cnt)
+#define GC_MF_SCATTER_ARGS (const uint8_t* src, uint64_t srcSize, uint32_t frameArg, uint32_t nTiles, uint32_t per, const uint32_t* offs, GcMfEntry* ent)
+#define GC_MF_VERIFY_ARGS  (const uint8_t* src, uint64_t srcSize, uint32_t frameArg, uint32_t nTiles, uint32_t per, const uint32_t* offs, const GcMfEntry* ent, uint32_t* rec)
+#define GC_MF_VSHORT_ARGS  (const uint8_t* src, uint64_t srcSize, uint32_t frameArg, uint32_t nTiles, uint32_t per, const uint32_t* offs, const GcMfEntry* ent, const uint32_t* recIn, uint32_t* recOut, const uint32_t* changedIn)
+#define GC_MF_GEOM_KERNELS(X, S) \
+    X(count[MF_BASE],    gc_mf_count_kernel##S,          GC_MF_COUNT_ARGS) \
+    X(count[MF_FAR],     gc_mf_count_far_kernel##S,      GC_MF_COUNT_ARGS) \
+    X(count[MF_SHORT],   gc_mf_count_short_kernel##S,    GC_MF_COUNT_ARGS) \
+    X(count[MF_FAR2],    gc_mf_count_far2_kernel##S,     GC_MF_COUNT_ARGS) \
+    X(scan,              gc_mf_scan_kernel##S,           (uint32_t* cnt, uint32_t tilesPerFrame)) \
+    X(scatter[MF_BASE],  gc_mf_scatter_kernel##S,        GC_MF_SCATTER_ARGS) \
+    X(scatter[MF_FAR],   gc_mf_scatter_far_kernel##S,    GC_MF_SCATTER_ARGS) \
+    X(scatter[MF_SHORT], gc_mf_scatter_short_kernel##S,  GC_MF_SCATTER_ARGS) \
+    X(scatter[MF_FAR2],  gc_mf_scatter_far2_kernel##S,   GC_MF_SCATTER_ARGS) \
+    X(link,              gc_mf_link_kernel##S,           (const uint32_t* offs, const GcMfEntry* ent, GcMfEntry* entOut, uint32_t tilesPerFrame, uint64_t frameBytes, uint32_t nLists, uint32_t* ticket)) \
+    X(verify[MF_BASE],   gc_mf_verify_kernel##S,         GC_MF_VERIFY_ARGS) \
+    X(verify[MF_FAR],    gc_mf_verify_far_kernel##S,     GC_MF_VERIFY_ARGS) \
+    X(verify[MF_FAR2],   gc_mf_verify_far2_kernel##S,    GC_MF_VERIFY_ARGS) \
+    X(verifyShort,       gc_mf_verify_short_kernel##S,   GC_MF_VSHORT_ARGS) \
+    X(verifyShortB,      gc_mf_verify_shortb_kernel##S,  GC_MF_VSHORT_ARGS) \
+    X(deepen,            gc_mf_deepen_kernel##S,         (const uint8_t* src, uint64_t srcSize, uint32_t frameArg, uint32_t nTiles, uint32_t per, uint32_t depths, const uint32_t* recIn, uint32_t* recOut, uint32_t* changed)) \
+    X(vparseTile,        gc_mf_vparse_tile_kernel##S,    (const uint8_t* src, uint64_t srcSize, uint32_t frameArg, uint32_t nTiles, uint32_t per, uint32_t lazy, const uint32_t* offs, const GcMfEntry* ent, GcSeqRaw* seqRaw, uint8_t* lit, GcBlockMeta* meta, uint32_t* ticket, uint32_t* tileWord, unsigned long long* prof))
+#define GC_MF_DECLARE(slot, kernel, params) extern "C" __global__ void kernel params;
+GC_MF_GEOM_KERNELS(GC_MF_DECLARE, )
+GC_MF_GEOM_KERNELS(GC_MF_DECLARE, _p8)
+
+// ... and the kernels that work on blocks, not tiles, and exist once: W6 and W6r (gc_lz_window.hip, which expands both lists again inside its namespace), W5s, W7 and the literal prices (gc_lz_price.hip), W7L (gc_lz_dpl.hip)
+#define GC_MF_W6_KERNELS \
+    extern "C" __global__ void gc_mf_ringparse_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t*, GcSeqRaw*, uint8_t*, GcBlockMeta*); \
+    extern "C" __global__ void gc_mf_parse_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, const uint32_t*, GcSeqRaw*, uint8_t*, GcBlockMeta*, uint16_t*, uint32_t);
+GC_MF_W6_KERNELS
+extern "C" __global__ void gc_mf_short_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, uint32_t, uint16_t*);
+extern "C" __global__ void gc_mf_litprice_kernel(const uint8_t*, uint64_t, uint32_t, uint32_t, const uint16_t*, uint32_t, uint8_t*);
+#define GC_MF_DP_ARGS  const uint8_t* src, uint64_t srcSize, uint32_t nBlocks, uint32_t per, uint32_t groupBlocks, uint32_t phase, uint32_t* dps, uint32_t litCtx, const uint32_t* rec, const uint16_t* rec3, const uint16_t* price, uint32_t* dp, uint32_t* winCost
+extern "C" __global__ void gc_mf_dp2_kernel(GC_MF_DP_ARGS);                             // W7, shortest piece 2 / 3 bytes
+extern "C" __global__ void gc_mf_dp3_kernel(GC_MF_DP_ARGS);
+extern "C" __global__ void gc_mf_dpl2_kernel(GC_MF_DP_ARGS, const uint8_t* litPrice);   // W7L, shortest piece 2 (dpl2) / 3 (dplz) bytes; dpl2s / dplzs: their phase A
+extern "C" __global__ void gc_mf_dpl2s_kernel(GC_MF_DP_ARGS, const uint8_t* litPrice);
+extern "C" __global__ void gc_mf_dplz_kernel(GC_MF_DP_ARGS, const uint8_t* litPrice);
+extern "C" __global__ void gc_mf_dplzs_kernel(GC_MF_DP_ARGS, const uint8_t* litPrice);
 
 // Workgroup index -> work item such that each of the 8 XCDs (workgroups are dealt round-robin to XCDs) owns one contiguous
 // range of items: neighbouring tiles / blocks then share an L2.  The grid is 8 * per workgroups, per = ceil(n / 8).

@@ -65,3 +65,15 @@ struct GcZdPlace { uint64_t dst; uint32_t rep[3]; uint32_t skip; };
 #define GC_ZD_UNSUPPORTED 3u      // dictionary id, offsets of 2 GiB and more
 #define GC_ZD_CHECKSUM    4u
 #define GC_ZD_SIZE        5u      // content size field does not match
+
+// The decoder's launches (gc_zstd_dec.hip), called by gc_zstd_decompress_device (gc_api.hip).  They take a stream: include this file after the HIP runtime (or its emulator stand-in).
+extern "C" void gc_zstd_dec_launch_index(hipStream_t st, const uint8_t* src, const GcZdFrame* frames, uint32_t nFrames, GcZdBlock* blocks, uint64_t* frameTot);
+extern "C" void gc_zstd_dec_launch_literals(hipStream_t st, const uint8_t* src, uint64_t srcSize, const GcZdFrame* frames, GcZdBlock* blocks, uint32_t nBlocks, uint8_t* litWork, unsigned long long* prof, const uint32_t* order, uint32_t* ready);
+extern "C" void gc_zstd_dec_launch_sequences(hipStream_t st, const uint8_t* src, uint64_t srcSize, const GcZdFrame* frames, GcZdBlock* blocks, uint32_t nBlocks, void* seqWork, unsigned long long* prof, const uint32_t* order, uint32_t* ready, int several);
+extern "C" void gc_zstd_dec_launch_exec(hipStream_t st, const uint8_t* src, uint64_t srcSize, uint8_t* dst, uint64_t dstCap, const GcZdFrame* frames, uint32_t nFrames, GcZdBlock* blocks, uint32_t* ticket,
+                                        uint8_t* litWork, uint64_t litWorkSize, void* seqWork, uint64_t* result, unsigned long long* prof, const uint32_t* ready, const uint8_t* dict, uint32_t dictSize);
+extern "C" void gc_zstd_dec_launch_place(hipStream_t st, const GcZdFrame* frames, uint32_t nFrames, const GcZdBlock* blocks, uint64_t dstCap, GcZdPlace* place, uint64_t* result, uint32_t* ferr);
+extern "C" void gc_zstd_dec_launch_spread(hipStream_t st, const uint8_t* src, uint64_t srcSize, uint8_t* dst, const GcZdFrame* frames, const GcZdBlock* blocks, uint32_t nBlocks, const GcZdPlace* place,
+                                          const uint8_t* litWork, uint64_t litWorkSize, const void* seqWork, uint32_t* ptr, uint64_t batchBase, uint32_t* ferr, const uint8_t* dict, uint32_t dictSize);
+extern "C" void gc_zstd_dec_launch_chase(hipStream_t st, uint8_t* dstBatch, uint32_t* ptr, uint32_t n, uint32_t hops, uint8_t* pieceDone, uint32_t* counter);
+extern "C" void gc_zstd_dec_launch_finish(hipStream_t st, const uint8_t* src, const uint8_t* dst, const GcZdFrame* frames, uint32_t nFrames, uint64_t* result, const uint32_t* ferr);

@@ -34,7 +34,6 @@
 // A raw-content dictionary of the context (gc_zstd_set_dictionary; DESIGN.md section 4 "Dictionaries") lies as history in front of every frame: offsets up to
 // produced + dictSize are sound, and a match byte whose source lies in front of the frame is a literal from the dictionary's buffer (dict == nullptr, dictSize 0: none).
 #include "gpucodec.h"
-#include "gc_zstd_dec.h"
 #include "gc_device.h"
 #ifdef HIPEMU
 #include "hip_runtime_stub.h"
@@ -43,6 +42,7 @@
 #define GC_LAUNCH(kernel, grid, block, stream, ...) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__)
 #endif
 #include <string.h>
+#include "gc_zstd_dec.h"      // (behind the runtime: its launch prototypes take a stream)
 
 // ---- format constants (RFC 8878 3.1.1.3.2.1.1: symbol -> baseline, extra bits) ----
 __constant__ uint32_t kZdLLBase[36] = { 0,1,2,3,4,5,6,7,8,9,10,11,12,13,14,15,16,18,20,22,24,28,32,40,48,64,128,256,512,1024,2048,4096,8192,16384,32768,65536 };

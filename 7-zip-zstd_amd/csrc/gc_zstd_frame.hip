@@ -17,8 +17,6 @@
 
 #define FRAME_T 256u
 
-struct GcFramePlan { uint64_t off; uint32_t size; uint32_t compressed; };
-
 __device__ __forceinline__ uint32_t frame_hdr_size(uint32_t frameLen) { return 5u + (frameLen < 256u ? 1u : (frameLen < 65536u + 256u ? 2u : 4u)); }
 // content length of the frame that block b belongs to
 __device__ __forceinline__ uint32_t frame_len_of(uint32_t b, uint32_t frameBlocks, uint64_t srcSize)
